@@ -7,9 +7,17 @@ cluster1d(f_dc) + opacity, the SH palette k-means (K = 65,536, 10 iterations), t
 cluster1d and the shN textures (the headline is the device pipeline).  The .sog
 container stage -- WebP lossless encode of the seven textures, CRC-32 and the ZIP layout
 (st_dev_sog_bundle_view, archive in pinned host memory) -- is timed right after on the same
-textures and reported in "container" with the end-to-end rate.
+textures (--full) and reported in "container" with the end-to-end rate.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--splats S] [--total-splats T] [--merge F]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR]
+                    [--splats S] [--total-splats T] [--merge F]
+
+A plain run builds the table, runs W warm-up steps, times K steps, writes the last step's outputs
+with --dump-outputs DIR (the seven textures' bytes, sampled above 2M bytes, and the meta fields, as
+DIR/<name>.npy; the table, the draws and the sampled positions are seeded, so two builds compare
+file for file) and prints the result line.  Everything else described here -- the container and
+end-to-end records, the stage table, the extra records, the verification, the CPU baseline -- runs
+only with --full, after the timed steps.
 
 Workloads (BASELINE.json configs):
   default (every N)     north_star's workload: ONE 10M-splat SH-3 table (seed 1002), strong-scaled
@@ -35,8 +43,8 @@ rank takes its global row range of them, so a T-splat table is the same table fo
 `textures_sha256` does not depend on N); 10M splats per GPU is block `rank`.
 
 Prints ONE JSON line (rank 0) with the roofline of the dominant kernel (the MFMA assign
-sweep, measured with HIP events on its own stream), the CPU-oracle baseline timed on a
-bounded sample, and the verification of the last step's output.
+sweep, measured with HIP events on its own stream) and, with --full, the CPU-oracle baseline
+timed on a bounded sample and the verification of the last step's output.
 """
 import argparse
 import json
@@ -56,6 +64,13 @@ def parse(argv=None):
     ap.add_argument('--gpus', type=int, default=1)
     ap.add_argument('--steps', type=int, default=3)
     ap.add_argument('--warmup', type=int, default=1)
+    ap.add_argument('--full', action='store_true',
+                    help='after the timed steps also run everything else the bench measures or checks: the stage-marked '
+                         'step, the output verification, the extra records, the .sog container, the PLY file -> .sog '
+                         'file job, the config-3 stage table and the CPU baseline (each has its own --no-... switch)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write what the last timed step returned (the seven textures, sampled, and the meta fields) '
+                         'as DIR/<name>.npy')
     ap.add_argument('--splats', type=int, default=None, help='splats per GPU (weak scaling; default 10M at N = 1)')
     ap.add_argument('--total-splats', type=int, default=None,
                     help='one table of this many splats split over the ranks (default 50M at N > 1: config 4)')
@@ -822,6 +837,35 @@ def textures_digest(tex, meta):
     return h.hexdigest()
 
 
+DUMP_SAMPLE = 2_000_000  # texels' bytes kept of a larger texture: 7 x 8 MB of float32, under 64 MB in all
+META_INTS = ('width', 'height', 'sh_bands', 'palette_size', 'shn_width', 'shn_height')
+META_ARRAYS = ('means_min', 'means_max', 'scales_codebook', 'sh0_codebook', 'shn_codebook')
+
+
+def dump_outputs(d, tex, meta, used, seed=20240):
+    """--dump-outputs: what the step handed its caller, as DIR/<name>.npy -- each of the seven
+    textures' bytes as float32 (a texture of more than DUMP_SAMPLE bytes: the bytes at DUMP_SAMPLE
+    positions drawn from a generator seeded by `seed` and the texture's place in TEX_ORDER, so the
+    same positions in every run over a table of that size), and the meta fields and the number of
+    Math.random draws the step consumed as float64"""
+    import numpy as np
+    import torch
+    os.makedirs(d, exist_ok=True)
+    for i, k in enumerate(TEX_ORDER):
+        if k not in tex:
+            continue
+        t = tex[k].view(-1)
+        if t.numel() > DUMP_SAMPLE:
+            idx = np.random.default_rng(seed + i).integers(0, t.numel(), DUMP_SAMPLE)
+            t = t[torch.from_numpy(idx).to(t.device)]
+        np.save(os.path.join(d, k + '.npy'), t.cpu().numpy().astype(np.float32))
+    if meta is not None:
+        np.save(os.path.join(d, 'meta_geometry.npy'), np.array([int(getattr(meta, f)) for f in META_INTS], np.float64))
+        for f in META_ARRAYS:
+            np.save(os.path.join(d, 'meta_' + f + '.npy'), np.array(list(getattr(meta, f)), np.float64))
+    np.save(os.path.join(d, 'draws_used.npy'), np.array([used], np.float64))
+
+
 _PHASE = ['start']
 
 
@@ -990,10 +1034,14 @@ def main(args):
         kstats[name] = {'avg_ms': ms / max(cnt, 1), 'launches': cnt}
     ctx.set_profiling(False)
     n_local = sum(t['x'].shape[0] for t in tabs)
+    if args.dump_outputs and rank == 0:
+        progress('writing the outputs')
+        dump_outputs(args.dump_outputs, tex, meta, used)
+    full = args.full  # everything below the timed steps that is not the headline's own arithmetic
 
     # one more step with per-stage event marks (outside the timed region; single device only)
     stages = None
-    if not sharded:
+    if full and not sharded:
         os.environ['ST_TIMING'] = '1'
         step()
         torch.cuda.synchronize()
@@ -1002,8 +1050,8 @@ def main(args):
 
     # the last timed step's output checked against the reference's definitions
     verification = None
-    progress('stage table and verification')
-    if not args.no_verify:
+    if full and not args.no_verify:
+        progress('stage table and verification')
         if not sharded:
             verification = verify_step(ctx, tabs[0], tex, step, all_labels=not args.verify_sample)
         elif not args.dist_python:
@@ -1014,7 +1062,7 @@ def main(args):
     # extra records beside the main one (fewer steps; outside the main timed region)
     extras = {}
     main_default = not args.merge and args.splats is None and args.total_splats is None and not args.dist_python
-    if main_default and not args.no_extra:
+    if full and main_default and not args.no_extra:
         ks, kw = max(1, args.extra_steps), 1
         main_sha = textures_digest(tex, meta) if rank == 0 else None
 
@@ -1085,52 +1133,66 @@ def main(args):
         if verification and not verification['ok']:
             sys.exit(1)
         return
-    tex_sha = textures_digest(tex, meta)
+    tex_sha = textures_digest(tex, meta) if full else None
     # the RCCL the library's collectives run on (st_rccl_info; the same file under the Node host)
     # and torch.distributed's own copy
     rccl_version = rccl_path = rccl_torch = None
-    try:
-        rccl_version, rccl_path = sh.rccl_info()
-    except sh.StError as e:
-        rccl_path = f'not loadable: {e}'
-    try:
-        rccl_torch = '.'.join(map(str, torch.cuda.nccl.version()))
-    except Exception:
-        pass
+    if full:
+        try:
+            rccl_version, rccl_path = sh.rccl_info()
+        except sh.StError as e:
+            rccl_path = f'not loadable: {e}'
+        try:
+            rccl_torch = '.'.join(map(str, torch.cuda.nccl.version()))
+        except Exception:
+            pass
     # the .sog container of this step's textures on rank 0 (outside the headline's timed region)
-    addr0, size0 = ctx.dev_sog_bundle_view(meta, total, tex, 0, 0)  # warm: workspace + pinned archive
-    ref_archive = bytes((ctypes_char_array(size0)).from_address(addr0))
-    ctx.set_profiling(True)
-    ctx.reset_kernel_stats()
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    for _ in range(args.steps):
-        _, archive_bytes = ctx.dev_sog_bundle_view(meta, total, tex, 0, 0)
-    container_ms = (time.perf_counter() - t0) / args.steps * 1e3
-    ckern = {}
-    for name in ('webp.predict', 'webp.hist', 'webp.bits', 'webp.emit', 'crc32'):
-        ms, cnt = ctx.kernel_stats(name)
-        ckern[name] = ms / args.steps
-    ctx.set_profiling(False)
+    container = ref_archive = None
+    if full:
+        addr0, size0 = ctx.dev_sog_bundle_view(meta, total, tex, 0, 0)  # warm: workspace + pinned archive
+        ref_archive = bytes((ctypes_char_array(size0)).from_address(addr0))
+        ctx.set_profiling(True)
+        ctx.reset_kernel_stats()
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(args.steps):
+            _, archive_bytes = ctx.dev_sog_bundle_view(meta, total, tex, 0, 0)
+        container_ms = (time.perf_counter() - t0) / args.steps * 1e3
+        ckern = {}
+        for name in ('webp.predict', 'webp.hist', 'webp.bits', 'webp.emit', 'crc32'):
+            ms, cnt = ctx.kernel_stats(name)
+            ckern[name] = ms / args.steps
+        ctx.set_profiling(False)
+        container = {
+            'what': 'st_dev_sog_bundle_view: WebP lossless x7 + CRC-32 + ZIP of this step\'s textures, archive in '
+                    'pinned host memory (rank 0)',
+            'ms': container_ms,
+            'archive_bytes': archive_bytes,
+            'kernel_ms': ckern,
+            'end_to_end_ms_per_step': elapsed / args.steps * 1e3 + container_ms,
+            'end_to_end_Msplats_per_s': total / (elapsed / args.steps + container_ms / 1e3) / 1e6,
+        }
     value = total * args.steps / elapsed / 1e6
     avg_sweep_s = (sweep_ms / max(sweep_launches, 1)) / 1e3
     D = 45
     flops_per_launch = 2.0 * n_local * pal * D  # nearest-centroid dot products, one assign pass (this rank)
     achieved = flops_per_launch / avg_sweep_s / 1e12 if sweep_launches else None
     e2e = None
-    progress('end-to-end file run')
-    if not sharded and not args.no_e2e:
+    if full and not sharded and not args.no_e2e:
+        progress('end-to-end file run')
         e2e = end_to_end(ctx, tabs[0], args.iters, draws, tex, ref_archive, meta)
     paths = None
-    progress('config-3 stage table')
-    if not sharded and not args.no_paths:
+    if full and not sharded and not args.no_paths:
+        progress('config-3 stage table')
         # BASELINE config 3 (-r 0,45,0, filterNaN, Morton, chunk pack -> .compressed.ply) on its own
         # 10M SH-3 table: each HBM-bound stage priced by its algorithmic bytes (tools/bench_paths.py)
         sys.path.insert(0, os.path.join(ROOT, 'tools'))
         import bench_paths
         paths = bench_paths.measure(ctx, stream, dev, n=10_000_000, reps=5)
-    progress('CPU baseline (oracle on the host cores)')
-    cpu, cpu_all = (None, None) if (args.no_cpu_baseline or world > 1) else cpu_baseline(args)
+    cpu, cpu_all = None, None
+    if full and not args.no_cpu_baseline and world == 1:
+        progress('CPU baseline (oracle on the host cores)')
+        cpu, cpu_all = cpu_baseline(args)
     progress('writing the result')
     # HBM bytes per sweep launch from the committed rocprofv3 PMC passes (FETCH_SIZE x 2 + WRITE_SIZE
     # at this launch shape; tools/pmc_traffic.sh) -- PMC counters cannot be read from inside this run
@@ -1191,15 +1253,8 @@ def main(args):
         },
         'cpu_baseline': cpu,
         'cpu_baseline_all_cores': cpu_all,
-        'container': {
-            'what': 'st_dev_sog_bundle_view: WebP lossless x7 + CRC-32 + ZIP of this step\'s textures, archive in '
-                    'pinned host memory (rank 0)',
-            'ms': container_ms,
-            'archive_bytes': archive_bytes,
-            'kernel_ms': ckern,
-            'end_to_end_ms_per_step': elapsed / args.steps * 1e3 + container_ms,
-            'end_to_end_Msplats_per_s': total / (elapsed / args.steps + container_ms / 1e3) / 1e6,
-        },
+        'full': full,
+        'container': container,
         'end_to_end_file': e2e,
         'paths_config3': paths,
         'stages_ms': stages,

@@ -147,12 +147,50 @@ def test_table_rows_independent_of_the_split():
     assert all(torch.equal(blk0[k], r1[k]) for k in blk0)
 
 
+def test_dump_outputs_writes_the_steps_outputs_as_float_arrays(tmp_path, monkeypatch):
+    """--dump-outputs: every texture and meta field as a float .npy; a texture above DUMP_SAMPLE
+    bytes is sampled at positions that depend on its size and place only, so two runs (two builds)
+    write arrays that compare element for element"""
+    import types
+
+    import numpy as np
+    import torch
+
+    import bench
+    monkeypatch.setattr(bench, 'DUMP_SAMPLE', 1000)
+    assert not bench.parse([]).full and bench.parse(['--full', '--dump-outputs', 'd']).dump_outputs == 'd'
+    g = torch.Generator().manual_seed(3)
+    tex = {k: torch.randint(0, 256, (600 if k == 'shN_centroids' else 4000,), dtype=torch.uint8, generator=g)
+           for k in bench.TEX_ORDER}
+    meta = types.SimpleNamespace(width=40, height=25, sh_bands=3, palette_size=150, shn_width=960, shn_height=3,
+                                 means_min=[-1.5, 0.0, 2.0], means_max=[1.0, 2.0, 3.5],
+                                 scales_codebook=[i / 7 for i in range(256)], sh0_codebook=[-i / 3 for i in range(256)],
+                                 shn_codebook=[i * 0.001 for i in range(256)])
+    a, b = tmp_path / 'a', tmp_path / 'b'
+    bench.dump_outputs(str(a), tex, meta, 1234)
+    changed = dict(tex, quats=tex['quats'].clone())
+    changed['quats'] ^= 1  # every byte differs: whatever the sample holds, it shows
+    bench.dump_outputs(str(b), changed, meta, 1234)
+    names = sorted(os.listdir(a))
+    assert names == sorted([k + '.npy' for k in bench.TEX_ORDER] + ['meta_geometry.npy', 'draws_used.npy'] +
+                           ['meta_' + f + '.npy' for f in bench.META_ARRAYS])
+    for n in names:
+        x, y = np.load(a / n), np.load(b / n)
+        assert x.dtype in (np.float32, np.float64) and x.shape == y.shape
+        assert np.array_equal(x, y) == (n != 'quats.npy'), n
+    assert np.load(a / 'means_l.npy').shape == (1000,)
+    assert np.array_equal(np.load(a / 'shN_centroids.npy'), tex['shN_centroids'].numpy().astype(np.float32))
+    assert np.load(a / 'meta_geometry.npy').tolist() == [40, 25, 3, 150, 960, 3]
+    assert np.load(a / 'meta_means_max.npy').tolist() == [1.0, 2.0, 3.5]
+    assert np.load(a / 'draws_used.npy').tolist() == [1234.0]
+
+
 @pytest.mark.gpu
 def test_self_launched_two_ranks_match_one_gpu(tmp_path):
     """`bench.py --gpus 2 --backend gloo` (no torchrun on the command line) rehearsed on one GPU:
     two processes running the library's st_dev_sog_sharded over its host shared-memory transport,
     and the textures of the 4M-splat table equal one GPU's"""
-    common = ['--steps', '1', '--warmup', '0', '--no-cpu-baseline', '--no-e2e', '--no-paths']
+    common = ['--steps', '1', '--warmup', '0', '--full', '--no-cpu-baseline', '--no-e2e', '--no-paths']
     env = dict(os.environ, PYTHONUNBUFFERED='1')
     r2 = subprocess.run([sys.executable, BENCH, '--gpus', '2', '--backend', 'gloo', '--no-weak',
                          '--splats', '2000000'] + common, capture_output=True, text=True, timeout=600, env=env)

@@ -35,7 +35,7 @@ sys.path.insert(0, os.path.join(ROOT, 'oracle'))
 
 pytestmark = pytest.mark.gpu
 
-COMMON = ['--steps', '1', '--warmup', '0', '--no-cpu-baseline', '--no-e2e', '--no-paths', '--no-extra']
+COMMON = ['--steps', '1', '--warmup', '0', '--full', '--no-cpu-baseline', '--no-e2e', '--no-paths', '--no-extra']
 ITERS = 10
 
 

@@ -5,10 +5,12 @@ Pinned by tests/golden/sog_bundle.* -- the reference's own writeSog writing a .s
 (serialize/zip-writer.ts, crc.ts, write-sog.ts:271-366) with a fixed clock; its
 entries hold the identity WebP stand-in's payload (tests/golden/gen/build_ref.py).
 """
+import atexit
 import io
 import os
 import shutil
 import subprocess
+import tempfile
 import zipfile
 import zlib
 
@@ -108,7 +110,7 @@ def test_js_number_formatting_edge_values():
 
 
 # ---- VP8L header / prefix codes (product host code) + a scalar emulation of the kernels
-HARNESS = '/tmp/st_vp8l_cpu_check'
+_HARNESS = []  # built once per session into a directory of its own (removed at exit)
 
 
 def _harness():
@@ -116,10 +118,13 @@ def _harness():
     lib_src = os.path.join(ROOT, 'splat-transform_amd', 'csrc', 'st_vp8l.cpp')
     if shutil.which('g++') is None:
         pytest.skip('g++ not available')
-    if not os.path.exists(HARNESS) or os.path.getmtime(HARNESS) < max(os.path.getmtime(src),
-                                                                     os.path.getmtime(lib_src)):
-        subprocess.check_call(['g++', '-O2', '-std=c++17', '-o', HARNESS, src, lib_src])
-    return HARNESS
+    if not _HARNESS:
+        d = tempfile.mkdtemp(prefix='st_vp8l_')
+        atexit.register(shutil.rmtree, d, ignore_errors=True)
+        exe = os.path.join(d, 'vp8l_cpu_check')
+        subprocess.check_call(['g++', '-O2', '-std=c++17', '-o', exe, src, lib_src])
+        _HARNESS.append(exe)
+    return _HARNESS[0]
 
 
 def _roundtrip(img, tmp_path, cache_bits=-1, want_bits=None):

@@ -5,7 +5,7 @@
 # Outputs go under gpurun_out/<tag>_*; every GPU step runs under its own time limit and the first
 # failure ends the call (the log's tail is printed).
 #   suite    the whole GPU suite, then smoke() (the round-end driver's two steps)
-#   bench    the driver's bench command (bench.py --gpus 1 --steps 20 --warmup 5), summary line
+#   bench    the whole bench line (bench.py --gpus 1 --steps 20 --warmup 5 --full), summary line
 #   prof     the same command under rocprofv3 --kernel-trace --stats (no extra records, no CPU
 #            baseline: their launches would mix into the sweep's average)
 #   pmc      the sweep's HBM traffic passes + utilisation passes, the fix-up's counter passes
@@ -39,7 +39,7 @@ for step in "$@"; do
       || fail smoke ${O}_smoke.log
     tail -2 ${O}_smoke.log ;;
   bench)
-    timeout -k 10 900 python3 bench.py --gpus 1 --steps 20 --warmup 5 > ${O}_bench.json 2> ${O}_bench.err \
+    timeout -k 10 900 python3 bench.py --gpus 1 --steps 20 --warmup 5 --full > ${O}_bench.json 2> ${O}_bench.err \
       || fail bench ${O}_bench.err
     python3 -c "
 import json; r = json.load(open('${O}_bench.json'))
@@ -53,7 +53,7 @@ print('realistic', rr.get('ms_per_step'), rr.get('vs_main_step'), rr.get('verifi
   prof)
     rm -rf ${O}_prof
     timeout -k 10 700 rocprofv3 --kernel-trace --stats -d ${O}_prof -o bench --output-format csv -- \
-      python3 bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --no-extra > ${O}_prof.json 2> ${O}_prof.err \
+      python3 bench.py --gpus 1 --steps 20 --warmup 5 --full --no-cpu-baseline --no-extra > ${O}_prof.json 2> ${O}_prof.err \
       || fail prof ${O}_prof.err
     echo profiled ;;
   pmc)
@@ -76,7 +76,7 @@ print('realistic', rr.get('ms_per_step'), rr.get('vs_main_step'), rr.get('verifi
       done
     done ;;
   dist1)
-    timeout -k 10 300 python3 bench.py --dist --total-splats 1250000 --steps 3 --warmup 1 --no-cpu-baseline --no-e2e \
+    timeout -k 10 300 python3 bench.py --dist --total-splats 1250000 --steps 3 --warmup 1 --full --no-cpu-baseline --no-e2e \
       --no-paths --no-extra > ${O}_dist1.json 2> ${O}_dist1.err || fail dist1 ${O}_dist1.err
     python3 -c "
 import json; r = json.load(open('${O}_dist1.json'))
@@ -100,7 +100,7 @@ print('dist1', round(r['ms_per_step'], 2), r['transport'], r['torch_backend'], r
   ab)
     for i in 1 2 3 4; do
       for v in base new; do
-        ST_LIB=tools/ab/$v.so timeout -k 10 300 python3 bench.py --steps 10 --warmup 2 --no-cpu-baseline --no-e2e \
+        ST_LIB=tools/ab/$v.so timeout -k 10 300 python3 bench.py --steps 10 --warmup 2 --full --no-cpu-baseline --no-e2e \
           --no-paths --no-extra --no-verify $AB_ARGS > ${O}_ab_$v$i.json 2> ${O}_ab_$v$i.err || fail ab ${O}_ab_$v$i.err
         python3 -c "import json; b=json.load(open('${O}_ab_$v$i.json')); k=b['kernels']; print('$v', $i, round(b['ms_per_step'], 2), b['textures_sha256'][:12], 'fixrow', round(k['kn.fixrow']['avg_ms'], 3), 'sweep', round(k['kn.sweep']['avg_ms'], 2))"
       done
@@ -110,7 +110,7 @@ print('dist1', round(r['ms_per_step'], 2), r['transport'], r['torch_backend'], r
     for i in 1 2 3 4; do
       for v in base env; do
         e=""; [ $v = env ] && e="$AB_ENV"
-        env $e timeout -k 10 300 python3 bench.py --steps 10 --warmup 2 --no-cpu-baseline --no-e2e \
+        env $e timeout -k 10 300 python3 bench.py --steps 10 --warmup 2 --full --no-cpu-baseline --no-e2e \
           --no-paths --no-extra --no-verify $AB_ARGS > ${O}_abe_$v$i.json 2> ${O}_abe_$v$i.err || fail abenv ${O}_abe_$v$i.err
         python3 -c "import json; b=json.load(open('${O}_abe_$v$i.json')); k=b['kernels']; print('$v', $i, round(b['ms_per_step'], 2), b['textures_sha256'][:12], 'fixrow', round(k['kn.fixrow']['avg_ms'], 3), 'sweep', round(k['kn.sweep']['avg_ms'], 2))"
       done

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Per-step kernel time of the library from a rocprofv3 trace directory (sqlite .db or csv) of
-`bench.py --steps 1 --warmup 0 --no-verify ...` (the timed step plus the stage-marked step =
+`bench.py --full --steps 1 --warmup 0 --no-verify ...` (the timed step plus the stage-marked step =
 2 steps).  Prints the top kernels (ms per step) and the memory-copy totals.
     python tools/step_breakdown.py gpurun_out/prof_single [steps=2]"""
 import glob
