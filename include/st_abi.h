@@ -43,6 +43,13 @@
  *     _forget)                              until the host asks for them
  *   st_dev_ply_transpose                    (the same, rows already in HBM)     read-ply.ts:165-182
  *   st_decompress_ply / st_dev_...          decompressPly                       readers/decompress-ply.ts:82-232
+ *   st_splat_layout / st_splat_read /       readSplat                           readers/read-splat.ts:14-148
+ *     st_dev_splat_read / _decode             (size checks :21-29, row decode :71-138)
+ *   st_ksplat_layout / st_ksplat_read /     readKsplat                          readers/read-ksplat.ts:103-384
+ *     st_dev_ksplat_read / _decode            (headers and section views :111-232, :371;
+ *                                             record decode :255-366, decodeFloat16 :29-60)
+ *   st_spz_layout / st_spz_read /           readSpz after its gunzip            readers/read-spz.ts:62-241
+ *     st_dev_spz_read / _decode               (header and plane views :65-107, decode :139-232)
  *   st_process                              processDataTable(dataTable, actions) process.ts:64-145
  *   st_ply_compressed_ply / st_ply_sog_bundle  readPly + processDataTable + writer, resident
  *                                           (the CLI's one-input path)           index.ts:463-496
@@ -562,6 +569,49 @@ int st_dev_decompress_ply(st_ctx *ctx, uint64_t n, const float *const *chunk, co
                           const uint8_t *const *sh, int32_t nsh, float *const *out);
 int st_decompress_ply(st_ctx *ctx, uint64_t n, const float *const *chunk, const uint32_t *const *vertex,
                       const uint8_t *const *sh, int32_t nsh, float *const *out);
+
+/* ---- the other input formats: .splat, .ksplat, .spz (index.ts:52-76) ----------
+ * Each reader decodes packed per-splat records into 14 + nsh float32 columns in its own order:
+ * x y z scale_0..2 f_dc_0..2 opacity rot_0..3 f_rest_0..nsh-1 (nsh = 0, 9, 24 or 45).
+ *
+ * st_*_layout are host-only (no context, no GPU).  They check what the reference checks, in its
+ * order, and return the row count and nsh; an input the reference throws on returns ST_ERR_ARG
+ * (ST_ERR_UNSUPPORTED for a version or compression mode it does not know) with the reference's
+ * message in st_last_error() -- for the RangeErrors of its typed-array views, V8's text.  They
+ * are the only gate before a launch: every decode and read call runs them first, and after ST_OK
+ * no kernel reads a byte outside the `len` bytes it was given, whatever the file says.
+ *   .splat   needs the file size only (a multiple of 32, not 0).
+ *   .ksplat  data = the file (at least its main header and section headers).  One deviation: a
+ *            section whose harmonics degree is above 3 is refused (the reference fails on the
+ *            first record of a non-empty one and loses track of its offsets after an empty one).
+ *   .spz     data = the INFLATED stream ("NGSP"...): gunzip is the caller's (the reference hands
+ *            it to the platform's DecompressionStream, read-spz.ts:16-28).  A degree above 3 gives
+ *            nsh = 0, as the reference's table lookup does.
+ * st_dev_*_decode: record bytes already in HBM -> device columns, on the context stream.
+ *   splat    rows: nrows 32-byte rows, 16-byte aligned.
+ *   ksplat   file: the whole file in HBM (4-byte aligned), len bytes; headers: a HOST copy of its
+ *            first headers_len bytes, covering at least the main and section headers -- the
+ *            section walk and the partial-bucket walk (read-ksplat.ts:196-269) run on the host.
+ *            When headers_len does not reach a section's partial bucket sizes they are copied
+ *            down from HBM (one small synchronous copy per such section).
+ *   spz      file: the inflated stream in HBM (4-byte aligned); its 16-byte header is read back.
+ * st_*_read write host columns, st_dev_*_read device columns (both return when the columns are
+ * complete).  .splat comes from a file descriptor: its rows stream page cache -> pinned double
+ * buffer -> HBM -> decode in st_dev_ply_read's chunks.  .ksplat / .spz come from a host buffer
+ * (the file, the inflated stream), uploaded once. */
+int st_splat_layout(uint64_t file_size, uint64_t *n, int32_t *nsh);
+int st_ksplat_layout(const uint8_t *data, uint64_t len, uint64_t *n, int32_t *nsh);
+int st_spz_layout(const uint8_t *data, uint64_t len, uint64_t *n, int32_t *nsh);
+int st_dev_splat_decode(st_ctx *ctx, const uint8_t *rows, uint64_t nrows, float *const *cols);
+int st_dev_ksplat_decode(st_ctx *ctx, const uint8_t *headers, uint64_t headers_len, const uint8_t *file, uint64_t len,
+                         float *const *cols);
+int st_dev_spz_decode(st_ctx *ctx, const uint8_t *file, uint64_t len, float *const *cols);
+int st_splat_read(st_ctx *ctx, int32_t fd, float *const *host_cols);
+int st_dev_splat_read(st_ctx *ctx, int32_t fd, float *const *cols);
+int st_ksplat_read(st_ctx *ctx, const uint8_t *data, uint64_t len, float *const *host_cols);
+int st_dev_ksplat_read(st_ctx *ctx, const uint8_t *data, uint64_t len, float *const *cols);
+int st_spz_read(st_ctx *ctx, const uint8_t *data, uint64_t len, float *const *host_cols);
+int st_dev_spz_read(st_ctx *ctx, const uint8_t *data, uint64_t len, float *const *cols);
 
 #ifdef __cplusplus
 }

@@ -379,6 +379,13 @@ struct ChunkSink {
 };
 void ply_read_dev(st_ctx *c, int fd, const st_ply_header &h, int element, void *const *cols,
                   ChunkSink *sink = nullptr);
+// the chunk loop of ply_read_dev for any file of fixed-size rows (the .splat reader, st_readers.hip):
+// `count` rows of R bytes at file offset `off` go page cache -> pinned double buffer -> HBM in
+// chunks of whole multiples of RB rows; run(rows, nr, row) queues the work on a staged chunk
+// (device rows, their count, the index of the first); short_msg: the error of a short file
+void stream_rows_dev(st_ctx *c, int fd, uint64_t off, uint64_t count, uint64_t R, uint32_t RB,
+                     const std::function<void(const uint8_t *, uint64_t, uint64_t)> &run, ChunkSink *sink,
+                     const char *short_msg);
 // st_ply_read: into the caller's host columns, and the element's mirrors (st_ctx::HostMirror)
 void ply_read_host(st_ctx *c, int fd, const st_ply_header &h, int element, void *const *host_cols, bool lazy = false);
 // st_ply_materialize: the lazy mirrors among these host columns copied down and dropped (upload()

@@ -317,13 +317,25 @@ void ply_read_dev(st_ctx *c, int fd, const st_ply_header &h, int element, void *
     for (int e = 0; e < element; ++e) off += h.elements[e].count * row_bytes(h.elements[e]);
     const st_ply_element &el = h.elements[element];
     Transposer tp(c, el, cols, "ply");
-    const uint64_t R = tp.R, total = el.count * R;
+    stream_rows_dev(
+        c, fd, off, el.count, tp.R, tp.RB,
+        [&](const uint8_t *rows, uint64_t nr, uint64_t row) { tp.run(rows, nr, row); }, sink,
+        "ply: file shorter than its header declares");
+}
+
+// `count` rows of R bytes at file offset `off` (fd) through pinned chunks into HBM: run(rows, nr,
+// row) is queued on the context stream for each staged chunk (device rows [row, row + nr) of the
+// element; chunks are whole multiples of RB rows); a sink also gets every chunk on the host
+void stream_rows_dev(st_ctx *c, int fd, uint64_t off, uint64_t count, uint64_t R, uint32_t RB,
+                     const std::function<void(const uint8_t *, uint64_t, uint64_t)> &run, ChunkSink *sink,
+                     const char *short_msg) {
+    const uint64_t total = count * R;
     if (!total) return;
     // chunks of whole LDS blocks, ~64 MiB (ST_PLY_CHUNK overrides the byte target: tests)
     uint64_t target = 64ull << 20;
     if (const char *e = std::getenv("ST_PLY_CHUNK")) target = std::strtoull(e, nullptr, 10);
-    const uint64_t per = (uint64_t)tp.RB * R;
-    const uint64_t chunk_rows = (target / per > 0 ? target / per : 1) * tp.RB;
+    const uint64_t per = (uint64_t)RB * R;
+    const uint64_t chunk_rows = (target / per > 0 ? target / per : 1) * RB;
     const uint64_t chunk_bytes = chunk_rows * R;
     uint8_t *pin = (uint8_t *)io_buf(c, 2 * (chunk_bytes + 64));
     uint8_t *stage[2] = {wsT<uint8_t>(c, "ply.stage0", chunk_bytes + 64), wsT<uint8_t>(c, "ply.stage1", chunk_bytes + 64)};
@@ -333,9 +345,9 @@ void ply_read_dev(st_ctx *c, int fd, const st_ply_header &h, int element, void *
     bool pending[2] = {false, false};
     try {
         uint64_t row = 0;
-        for (int k = 0; row < el.count; ++k) {
+        for (int k = 0; row < count; ++k) {
             const int b = k & 1;
-            const uint64_t nr = (el.count - row) < chunk_rows ? (el.count - row) : chunk_rows;
+            const uint64_t nr = (count - row) < chunk_rows ? (count - row) : chunk_rows;
             const uint64_t bytes = nr * R;
             uint8_t *hb = pin + b * (chunk_bytes + 64);
             if (pending[b]) ST_HIP(hipEventSynchronize(ev[b]));  // the copy out of hb is done
@@ -365,11 +377,11 @@ void ply_read_dev(st_ctx *c, int fd, const st_ply_header &h, int element, void *
             }
             for (auto &x : th) x.join();
             for (int t = 0; t < nt; ++t)
-                ST_REQUIRE(ok[t], ST_ERR_ARG, "ply: file shorter than its header declares");
+                ST_REQUIRE(ok[t], ST_ERR_ARG, short_msg);
             ST_HIP(hipMemcpyAsync(stage[b], hb, bytes, hipMemcpyHostToDevice, c->stream));
             ST_HIP(hipEventRecord(ev[b], c->stream));
             pending[b] = true;
-            tp.run(stage[b], nr, row);
+            run(stage[b], nr, row);
             if (sink) sink->take(b, hb, row, nr);
             row += nr;
         }

@@ -20,6 +20,7 @@ LIB_PATH = os.environ.get('ST_LIB') or os.path.join(PKG, 'lib', 'libsplat_hip.so
 
 ST_OK = 0
 ST_ERR_ARG, ST_ERR_HIP, ST_ERR_NONFINITE, ST_ERR_DRAWS = -1, -2, -3, -4
+ST_ERR_UNSUPPORTED = -6
 _lib = None
 
 
@@ -120,6 +121,9 @@ EXPORTS = [
     'st_group_sog_bundle_process',
     'st_transform_t', 'st_dev_transform_t', 'st_morton_order_t', 'st_dev_morton_order_t', 'st_sog_process',
     'st_sog_bundle_process', 'st_dev_sog_t',
+    'st_splat_layout', 'st_ksplat_layout', 'st_spz_layout', 'st_dev_splat_decode', 'st_dev_ksplat_decode',
+    'st_dev_spz_decode', 'st_splat_read', 'st_dev_splat_read', 'st_ksplat_read', 'st_dev_ksplat_read', 'st_spz_read',
+    'st_dev_spz_read',
 ]
 
 
@@ -516,6 +520,81 @@ def ply_parse_header(data):
     return h
 
 
+READER_COLS = ['x', 'y', 'z', 'scale_0', 'scale_1', 'scale_2', 'f_dc_0', 'f_dc_1', 'f_dc_2', 'opacity',
+               'rot_0', 'rot_1', 'rot_2', 'rot_3']
+
+
+def reader_columns(nsh):
+    """the column names of the .splat / .ksplat / .spz readers, in their order"""
+    return READER_COLS + [f'f_rest_{i}' for i in range(nsh)]
+
+
+def _layout(fn, *args):
+    n, nsh = ctypes.c_uint64(0), ctypes.c_int32(0)
+    check(fn(*args, ctypes.byref(n), ctypes.byref(nsh)))
+    return n.value, nsh.value
+
+
+def splat_layout(size):
+    """(rows, f_rest columns) of a .splat file of `size` bytes (read-splat.ts:21-29; host only)"""
+    return _layout(lib().st_splat_layout, ctypes.c_uint64(size))
+
+
+def ksplat_layout(data):
+    """(rows, f_rest columns) of a .ksplat file's bytes, checked as readKsplat checks them (host only)"""
+    data = bytes(data)
+    return _layout(lib().st_ksplat_layout, data, ctypes.c_uint64(len(data)))
+
+
+def spz_layout(data):
+    """(rows, f_rest columns) of an inflated .spz stream, checked as readSpz checks it (host only)"""
+    data = bytes(data)
+    return _layout(lib().st_spz_layout, data, ctypes.c_uint64(len(data)))
+
+
+def _is_compressed_ply(elements):
+    """isCompressedPly (decompress-ply.ts:7-78) over read_ply's [(element, {prop: column})]"""
+    if len(elements) not in (2, 3):
+        return False
+    el = {}
+    for name, cols in elements:  # Array.find: the first element of a name
+        el.setdefault(name, cols)
+
+    def shaped(cols, names, dt):
+        return all(k in cols and cols[k].dtype == dt for k in names)
+
+    chunk, vertex = el.get('chunk'), el.get('vertex')
+    if chunk is None or not shaped(chunk, CHUNK_COLS, np.float32):
+        return False
+    if vertex is None or not shaped(vertex, VERTEX_COLS, np.uint32):
+        return False
+    rows = lambda cols: len(next(iter(cols.values()))) if cols else 0
+    if (rows(vertex) + 255) // 256 != rows(chunk):
+        return False
+    if len(elements) == 3:
+        sh = el.get('sh')
+        if sh is None or len(sh) not in (9, 24, 45):
+            return False
+        if not shaped(sh, [f'f_rest_{i}' for i in range(len(sh))], np.uint8):
+            return False
+        if rows(sh) != rows(vertex):
+            return False
+    return True
+
+
+def spz_inflate(data):
+    """the gunzip of readSpz (read-spz.ts:50-75).  A file without the gzip magic is not inflated, and
+    the reference then sizes itself from its 4-byte magic buffer: whatever follows, it stops with
+    'invalid file header' or 'File too small to be valid .spz format'."""
+    data = bytes(data)
+    if data[:2] != b'\x1f\x8b':
+        if data[:4].ljust(4, b'\0') != b'NGSP':
+            raise StError(ST_ERR_ARG, 'invalid file header')
+        raise StError(ST_ERR_ARG, 'File too small to be valid .spz format')
+    import gzip
+    return gzip.decompress(data)
+
+
 def rccl_info():
     """(version, path) of the RCCL the library's collectives run on (st_rccl_info: loaded by path,
     /opt/rocm/lib/librccl.so.1 unless ST_RCCL says otherwise; no GPU needed)"""
@@ -887,6 +966,121 @@ class Context:
             return h.comment_list(), out
         finally:
             os.close(fd)
+
+    # ---- the other input formats (index.ts:52-76) ---------------------------------------
+    def _reader_out(self, n, nsh, device):
+        names = reader_columns(nsh)
+        if device is None:
+            cols = {k: np.empty(n, np.float32) for k in names}
+            ptrs = (ctypes.c_void_p * len(names))(*[cols[k].ctypes.data for k in names])
+        else:
+            import torch
+            cols = {k: torch.empty(n, dtype=torch.float32, device=device) for k in names}
+            ptrs = (ctypes.c_void_p * len(names))(*[cols[k].data_ptr() for k in names])
+        return cols, ptrs
+
+    def _read_splat(self, path, device):
+        fd = os.open(path, os.O_RDONLY)
+        try:
+            n, nsh = splat_layout(os.fstat(fd).st_size)
+            cols, ptrs = self._reader_out(n, nsh, device)
+            read = lib().st_splat_read if device is None else lib().st_dev_splat_read
+            check(read(self.h, ctypes.c_int32(fd), ptrs))
+            return cols
+        finally:
+            os.close(fd)
+
+    def _read_bytes(self, data, layout, host_fn, dev_fn, device):
+        n, nsh = layout(data)
+        cols, ptrs = self._reader_out(n, nsh, device)
+        check((host_fn if device is None else dev_fn)(self.h, data, ctypes.c_uint64(len(data)), ptrs))
+        return cols
+
+    def read_splat(self, path):
+        """readSplat (read-splat.ts:14-148) -> {name: float32 numpy column} in the reader's order; the
+        rows stream through HBM in st_dev_ply_read's chunks"""
+        return self._read_splat(path, None)
+
+    def read_splat_dev(self, path, device='cuda'):
+        """readSplat into device columns (torch tensors)"""
+        return self._read_splat(path, device)
+
+    def read_ksplat(self, path):
+        """readKsplat (read-ksplat.ts:103-384) -> {name: float32 numpy column}"""
+        with open(path, 'rb') as f:
+            data = f.read()
+        return self._read_bytes(data, ksplat_layout, lib().st_ksplat_read, lib().st_dev_ksplat_read, None)
+
+    def read_ksplat_dev(self, path, device='cuda'):
+        """readKsplat into device columns (torch tensors)"""
+        with open(path, 'rb') as f:
+            data = f.read()
+        return self._read_bytes(data, ksplat_layout, lib().st_ksplat_read, lib().st_dev_ksplat_read, device)
+
+    def read_spz(self, path):
+        """readSpz (read-spz.ts:49-241) -> {name: float32 numpy column}; the gunzip is Python's"""
+        with open(path, 'rb') as f:
+            data = spz_inflate(f.read())
+        return self._read_bytes(data, spz_layout, lib().st_spz_read, lib().st_dev_spz_read, None)
+
+    def read_spz_dev(self, path, device='cuda'):
+        """readSpz into device columns (torch tensors)"""
+        with open(path, 'rb') as f:
+            data = spz_inflate(f.read())
+        return self._read_bytes(data, spz_layout, lib().st_spz_read, lib().st_dev_spz_read, device)
+
+    def read_table(self, path):
+        """the CLI's input dispatch (index.ts:52-76) on the lower-cased file name: .ksplat, .splat,
+        .ply (decompressed when it is a compressed PLY, as decompress-ply.ts:35-80 tells), .spz ->
+        {name: numpy column} of the splat table"""
+        low = str(path).lower()
+        if low.endswith('.ksplat'):
+            return self.read_ksplat(path)
+        if low.endswith('.splat'):
+            return self.read_splat(path)
+        if low.endswith('.ply'):
+            _, els = self.read_ply(path)
+            el = dict(els)
+            if _is_compressed_ply(els):
+                shc = [el['sh'][f'f_rest_{i}'] for i in range(len(el['sh']))] if 'sh' in el else []
+                return self.decompress_ply(el['chunk'], el['vertex'], shc)
+            if 'vertex' not in el:
+                raise StError(ST_ERR_ARG, 'the PLY file has no vertex element')
+            return el['vertex']
+        if low.endswith('.spz'):
+            return self.read_spz(path)
+        raise StError(ST_ERR_UNSUPPORTED, f'Unsupported input file type: {path}')
+
+    @staticmethod
+    def _col_ptrs(out, nsh):
+        names = reader_columns(nsh)
+        return (ctypes.c_void_p * len(names))(*[out[k].data_ptr() for k in names])
+
+    def dev_splat_decode(self, rows, out):
+        """.splat rows already in HBM (uint8 tensor of n * 32 bytes, 16-byte aligned) -> `out`, a dict
+        of float32 tensors (reader_columns(0))"""
+        check(lib().st_dev_splat_decode(self.h, _ptr(rows), ctypes.c_uint64(rows.numel() // 32),
+                                        self._col_ptrs(out, 0)))
+
+    def dev_ksplat_decode(self, headers, file, out):
+        """a .ksplat file already in HBM (uint8 tensor) with a host copy of (at least) its headers
+        (bytes) -> `out` (reader_columns(nsh) of ksplat_layout)"""
+        headers = bytes(headers)
+        nsh = len(out) - 14
+        check(lib().st_dev_ksplat_decode(self.h, headers, ctypes.c_uint64(len(headers)), _ptr(file),
+                                         ctypes.c_uint64(file.numel()), self._col_ptrs(out, nsh)))
+
+    def dev_spz_decode(self, file, out):
+        """an inflated .spz stream already in HBM (uint8 tensor) -> `out` (reader_columns(nsh))"""
+        check(lib().st_dev_spz_decode(self.h, _ptr(file), ctypes.c_uint64(file.numel()),
+                                      self._col_ptrs(out, len(out) - 14)))
+
+    def dev_ply_transpose(self, header, element, rows, out):
+        """st_dev_ply_transpose: an element's rows already in HBM -> `out`, its property tensors in order"""
+        ptrs = (ctypes.c_void_p * max(len(out), 1))(*[t.data_ptr() for t in out])
+        nrows = rows.numel() // max(int(lib().st_ply_row_bytes(ctypes.byref(header), ctypes.c_int32(element))), 1)
+        check(lib().st_dev_ply_transpose(self.h, ctypes.byref(header), ctypes.c_int32(element), _ptr(rows),
+                                         ctypes.c_uint64(nrows), ptrs))
 
     def dev_decompress_ply(self, chunk, vertex, sh, out):
         """device form of decompress_ply: torch tensors in, `out` dict of float32 tensors (DECOMP_COLS + f_rest_*)"""
