@@ -67,6 +67,9 @@ struct Chain {
             if (k.name == nm) return true;
         return false;
     }
+    int coeffs() const {  // the band of the current columns
+        return band_coeffs([&](const char *nm) { return has(nm); });
+    }
     // the kernels read these by name from the float32 columns: a same-named column of another
     // type would be silently skipped (the reference reads any type through getRow)
     void require_f32(const std::string &nm, const char *what) const {
@@ -90,20 +93,8 @@ struct Chain {
     }
 };
 
-int band_coeffs(const std::vector<ChainCol> &cols) {
-    // { '9': 1, '24': 2, '-1': 3 }[shNames.findIndex(v => !dataTable.hasColumn(v))] ?? 0
-    int first_missing = -1;
-    for (int i = 0; i < 45 && first_missing < 0; ++i) {
-        const std::string nm = "f_rest_" + std::to_string(i);
-        bool hit = false;
-        for (auto &k : cols) hit = hit || k.name == nm;
-        if (!hit) first_missing = i;
-    }
-    return first_missing == 9 ? 3 : first_missing == 24 ? 8 : first_missing == -1 ? 15 : 0;
-}
-
 void run_actions(Chain &ch, const st_action *actions, int nactions) {
-    const int in_coeffs = band_coeffs(ch.cols);  // filterBands reads the ORIGINAL table (process.ts:111)
+    const int in_coeffs = ch.coeffs();  // filterBands reads the ORIGINAL table (process.ts:111)
     for (int a = 0; a < nactions; ++a) {
         const st_action &act = actions[a];
         switch (act.kind) {
@@ -164,7 +155,7 @@ const char *const SH_NAMES[45] = {
 void compressed_tail(Chain &ch, float *chunk, uint32_t *vertex, uint8_t *sh, int32_t *out_coeffs) {
     static const char *pcols[] = {"x", "y", "z", "scale_0", "scale_1", "scale_2", "f_dc_0",
                                   "f_dc_1", "f_dc_2", "opacity", "rot_0", "rot_1", "rot_2", "rot_3"};
-    const int C = band_coeffs(ch.cols);
+    const int C = ch.coeffs();
     *out_coeffs = C;
     if (ch.n == 0) return;
     const st_ttable *tt = ch.typed();
@@ -210,8 +201,7 @@ void upload_chain(st_ctx *c, const st_ttable *src, Chain &ch) {
     std::vector<HostXfer> up;
     for (int i = 0; i < src->ncol; ++i) {
         const int sz = type_size(src->types[i]);
-        void *d = ws(c, "chain.in." + std::to_string(i), src->n * sz + 16);
-        up.push_back(HostXfer{src->cols[i], d, src->n * sz});
+        void *d = ws_upload(c, "chain.in." + std::to_string(i), src->cols[i], src->n * sz, up);
         ch.cols.push_back(ChainCol{src->names[i], src->types[i], d});
     }
     staged_h2d(c, up);
@@ -237,34 +227,9 @@ void ply_chain(st_ctx *c, int fd, const st_ply_header *h, int element, Chain &ch
 // the processed table as the multi-GPU writeSog takes it: float32 columns by name (the sharded
 // path moves float32 columns only; a single device takes every type through sog_tdev)
 const st_table *sog_view(Chain &ch) {
-    static const char *scols[] = {"x", "y", "z", "scale_0", "scale_1", "scale_2", "f_dc_0", "f_dc_1", "f_dc_2",
-                                  "opacity", "rot_0", "rot_1", "rot_2", "rot_3"};
-    for (auto *nm : scols) ch.require_f32(nm, "multi-GPU writeSog");
-    for (int i = 0; i < 45; ++i) ch.require_f32("f_rest_" + std::to_string(i), "multi-GPU writeSog");
+    for (auto &nm : sog_columns()) ch.require_f32(nm, "multi-GPU writeSog");
     return ch.f32();
 }
-
-// device textures of writeSog for n rows of band C (workspace slots h.s.*)
-st_sog_textures sog_textures(st_ctx *c, uint64_t n, int C, uint64_t *tex_bytes, uint64_t *cen_bytes) {
-    int32_t W, H, pal, cw, chh;
-    ST_REQUIRE(st_sog_geometry(n, C, &W, &H, &pal, &cw, &chh) == ST_OK, ST_ERR_ARG, "sog: empty table");
-    const uint64_t tex = (uint64_t)W * H * 4;
-    st_sog_textures dt{};
-    dt.means_l = wsT<uint8_t>(c, "h.s.ml", tex);
-    dt.means_u = wsT<uint8_t>(c, "h.s.mu", tex);
-    dt.quats = wsT<uint8_t>(c, "h.s.q", tex);
-    dt.scales = wsT<uint8_t>(c, "h.s.sc", tex);
-    dt.sh0 = wsT<uint8_t>(c, "h.s.sh0", tex);
-    if (C) {
-        dt.shn_labels = wsT<uint8_t>(c, "h.s.shl", tex);
-        dt.shn_centroids = wsT<uint8_t>(c, "h.s.shc", (uint64_t)cw * chh * 4);
-    }
-    *tex_bytes = tex;
-    *cen_bytes = (uint64_t)cw * chh * 4;
-    return dt;
-}
-
-
 
 // ---- writeCompressedPly into a file (write-compressed-ply.ts:31-115 + the CLI's write) --------
 // the header text of write-compressed-ply.ts:35-54
@@ -400,86 +365,49 @@ uint64_t compressed_ply_to_file(st_ctx *c, uint64_t m, int C, const float *dchun
     return total - base;
 }
 
-#define ST_REQUIRE_RC(cond, msg)           \
-    do {                                   \
-        if (!(cond)) {                     \
-            set_last_error(msg);           \
-            return ST_ERR_ARG;             \
-        }                                  \
-    } while (0)
+// the host table into the chain
+auto host_loader(st_ctx *c, const st_ttable *src) {
+    return [=](Chain &ch) {
+        ST_ARG(c && src, "NULL argument");
+        check_src(src);
+        upload_chain(c, src, ch);
+    };
+}
 
-// processDataTable + writeSog on a table the loader puts in the chain: the .sog archive
-// (out / out_size) or the textures and meta on the host (tex_meta / tex_out).  One device takes
-// every column type (sog_tdev); with the st_set_devices group the processed float32 columns are
-// sharded over it from the host.
+// processDataTable + writeSog on a table the loader puts in the chain, into the sink.  One device
+// takes every column type (sog_tdev); with the st_set_devices group the processed float32 columns
+// are sharded over it from the host.
 template <typename Load>
-int sog_chain(st_ctx *c, Load load, const st_action *actions, int32_t nactions, int32_t iters, const double *draws,
-              uint64_t ndraws, uint64_t *used, uint16_t dos_time, uint16_t dos_date, uint8_t **out,
-              uint64_t *out_size, st_sog_meta *tex_meta, const st_sog_textures *tex_out) {
-    if (int rc = apply_env_devices()) return rc;
-    const auto group = default_group();  // held for the whole call
-    std::vector<std::vector<float>> host;  // multi-GPU: the processed columns, sharded from the host
-    std::vector<float *> hcols;
-    std::vector<std::string> hnames;
-    std::vector<const char *> hcn;
-    st_table ht{};
-    int rc = guard([&] {
-        ST_REQUIRE(c && ((out && out_size) || (tex_meta && tex_out)), ST_ERR_ARG, "NULL argument");
-        ST_REQUIRE(actions || nactions == 0, ST_ERR_ARG, "NULL argument");
-        use_device(c);
-        Chain ch{c};
-        load(ch);
-        run_actions(ch, actions, nactions);
-        if (group) {
-            const st_table *t = sog_view(ch);
-            std::vector<HostXfer> down;
-            for (int i = 0; i < t->ncol; ++i) {
-                host.emplace_back(t->n);
-                hnames.push_back(t->names[i]);
-                down.push_back(HostXfer{host.back().data(), t->cols[i], t->n * 4});
-            }
-            staged_d2h(c, down);
-            for (size_t i = 0; i < host.size(); ++i) hcols.push_back(host[i].data()), hcn.push_back(hnames[i].c_str());
-            ht = st_table{t->n, t->ncol, hcn.data(), hcols.data()};
-            return;
+void sog_chain(st_ctx *c, Load load, const st_action *actions, int32_t nactions, int32_t iters, const double *draws,
+               uint64_t ndraws, uint64_t *used, const SogSink &to) {
+    const auto group = sog_group();  // held for the whole call
+    ST_ARG(c && to.ok(), "NULL argument");
+    ST_ARG(actions || nactions == 0, "NULL argument");
+    use_device(c);
+    Chain ch{c};
+    load(ch);
+    run_actions(ch, actions, nactions);
+    if (group) {
+        const st_table *t = sog_view(ch);
+        std::vector<std::vector<float>> host;  // the processed columns, sharded from the host
+        std::vector<float *> hcols;
+        std::vector<HostXfer> down;
+        for (int i = 0; i < t->ncol; ++i) {
+            host.emplace_back(t->n);
+            down.push_back(HostXfer{host.back().data(), t->cols[i], t->n * 4});
         }
-        const int C = band_coeffs(ch.cols);
-        uint64_t tex, cbytes;
-        const st_sog_textures dt = sog_textures(c, ch.n, C, &tex, &cbytes);
-        st_sog_meta meta{};
-        const uint64_t u = sog_tdev(c, ch.typed(), iters, draws, ndraws, &meta, &dt);
-        if (tex_out) {
-            std::vector<HostXfer> down;
-            for (auto pr : {std::make_pair(tex_out->means_l, dt.means_l), std::make_pair(tex_out->means_u, dt.means_u),
-                            std::make_pair(tex_out->quats, dt.quats), std::make_pair(tex_out->scales, dt.scales),
-                            std::make_pair(tex_out->sh0, dt.sh0)}) {
-                ST_REQUIRE(pr.first, ST_ERR_ARG, "sog: texture output is NULL");
-                down.push_back(HostXfer{pr.first, pr.second, tex});
-            }
-            if (C) {
-                ST_REQUIRE(tex_out->shn_labels && tex_out->shn_centroids, ST_ERR_ARG, "sog: shN outputs are NULL");
-                down.push_back(HostXfer{tex_out->shn_labels, dt.shn_labels, tex});
-                down.push_back(HostXfer{tex_out->shn_centroids, dt.shn_centroids, cbytes});
-            }
-            staged_d2h(c, down);
-            *tex_meta = meta;
-        } else {
-            const uint8_t *view;
-            uint64_t nb;
-            sog_bundle_dev(c, meta, ch.n, dt, dos_time, dos_date, &view, &nb);
-            uint8_t *buf = (uint8_t *)std::malloc(nb);
-            ST_REQUIRE(buf, ST_ERR_NOMEM, "sog bundle: host allocation failed");
-            std::memcpy(buf, view, nb);
-            *out = buf;
-            *out_size = nb;
-        }
-        if (used) *used = u;
-    });
-    if (rc != ST_OK || !ht.ncol) return rc;
-    const st_table *tp = &ht;
-    if (tex_out) return st_group_sog(group.get(), &tp, 1, nullptr, iters, draws, ndraws, used, tex_meta, tex_out);
-    return st_group_sog_bundle(group.get(), &tp, 1, nullptr, iters, draws, ndraws, used, dos_time, dos_date, out,
-                               out_size);
+        staged_d2h(c, down);
+        for (auto &h : host) hcols.push_back(h.data());
+        const st_table ht{t->n, t->ncol, t->names, hcols.data()};
+        if (!ht.ncol) return;  // no float32 column left: nothing to shard
+        const st_table *tp = &ht;
+        return group_sog_to(group.get(), &tp, 1, nullptr, nullptr, nullptr, iters, draws, ndraws, used, to);
+    }
+    const st_sog_textures dt = sog_textures(c, ch.n, ch.coeffs());
+    st_sog_meta meta{};
+    const uint64_t u = sog_tdev(c, ch.typed(), iters, draws, ndraws, &meta, &dt);
+    sog_deliver(c, dt, meta, ch.n, to);
+    if (used) *used = u;
 }
 
 }  // namespace
@@ -543,7 +471,7 @@ int st_compressed_ply(st_ctx *c, const st_ttable *src, const st_action *actions,
         ST_REQUIRE(m == 0 || (chunk && vertex), ST_ERR_ARG, "compressed_ply: NULL output");
         auto *dchunk = wsT<float>(c, "chain.chunk", nch * 18);
         auto *dvert = wsT<uint32_t>(c, "chain.vert", m * 4);
-        const int Cmax = band_coeffs(ch.cols);
+        const int Cmax = ch.coeffs();
         auto *dsh = wsT<uint8_t>(c, "chain.sh", m * 3 * (uint64_t)Cmax + 1);
         int32_t C = 0;
         compressed_tail(ch, dchunk, dvert, dsh, &C);
@@ -572,7 +500,7 @@ int st_dev_compressed_ply(st_ctx *c, const st_ttable *src, const st_action *acti
         run_actions(ch, actions, nactions);
         ST_REQUIRE(ch.n == 0 || (chunk && vertex), ST_ERR_ARG, "compressed_ply: NULL output");
         int32_t C = 0;
-        if (band_coeffs(ch.cols) && ch.n) ST_REQUIRE(sh, ST_ERR_ARG, "compressed_ply: sh output is NULL");
+        if (ch.coeffs() && ch.n) ST_REQUIRE(sh, ST_ERR_ARG, "compressed_ply: sh output is NULL");
         compressed_tail(ch, chunk, vertex, sh, &C);
         *out_m = ch.n;
         *out_sh_coeffs = C;
@@ -593,7 +521,7 @@ int st_ply_compressed_ply(st_ctx *c, int32_t fd, const st_ply_header *h, int32_t
         ST_REQUIRE(m == 0 || (chunk && vertex), ST_ERR_ARG, "compressed_ply: NULL output");
         auto *dchunk = wsT<float>(c, "chain.chunk", nch * 18);
         auto *dvert = wsT<uint32_t>(c, "chain.vert", m * 4);
-        auto *dsh = wsT<uint8_t>(c, "chain.sh", m * 3 * (uint64_t)band_coeffs(ch.cols) + 1);
+        auto *dsh = wsT<uint8_t>(c, "chain.sh", m * 3 * (uint64_t)ch.coeffs() + 1);
         int32_t C = 0;
         compressed_tail(ch, dchunk, dvert, dsh, &C);
         ST_REQUIRE(C == 0 || m == 0 || sh, ST_ERR_ARG, "compressed_ply: sh output is NULL");
@@ -627,7 +555,7 @@ int st_ply_compressed_ply_file(st_ctx *c, int32_t fd, const st_ply_header *h, in
         const uint64_t m = ch.n, nch = (m + 255) / 256;
         auto *dchunk = wsT<float>(c, "chain.chunk", nch * 18);
         auto *dvert = wsT<uint32_t>(c, "chain.vert", m * 4);
-        auto *dsh = wsT<uint8_t>(c, "chain.sh", m * 3 * (uint64_t)band_coeffs(ch.cols) + 1);
+        auto *dsh = wsT<uint8_t>(c, "chain.sh", m * 3 * (uint64_t)ch.coeffs() + 1);
         int32_t C = 0;
         compressed_tail(ch, dchunk, dvert, dsh, &C);
         ST_HIP(hipStreamSynchronize(c->stream));
@@ -659,7 +587,7 @@ int st_compressed_ply_file(st_ctx *c, const st_ttable *src, const st_action *act
         const uint64_t m = ch.n, nch = (m + 255) / 256;
         auto *dchunk = wsT<float>(c, "chain.chunk", nch * 18);
         auto *dvert = wsT<uint32_t>(c, "chain.vert", m * 4);
-        auto *dsh = wsT<uint8_t>(c, "chain.sh", m * 3 * (uint64_t)band_coeffs(ch.cols) + 1);
+        auto *dsh = wsT<uint8_t>(c, "chain.sh", m * 3 * (uint64_t)ch.coeffs() + 1);
         int32_t C = 0;
         compressed_tail(ch, dchunk, dvert, dsh, &C);
         *size = compressed_ply_to_file(c, m, C, dchunk, dvert, dsh, out_fd, version);
@@ -671,37 +599,31 @@ int st_compressed_ply_file(st_ctx *c, const st_ttable *src, const st_action *act
 int st_ply_sog_bundle(st_ctx *c, int32_t fd, const st_ply_header *h, int32_t element, const st_action *actions,
                       int32_t nactions, int32_t iters, const double *draws, uint64_t ndraws, uint64_t *used,
                       uint16_t dos_time, uint16_t dos_date, uint8_t **out, uint64_t *out_size) {
-    return sog_chain(
-        c, [&](Chain &ch) {
-            ST_REQUIRE(c && h && fd >= 0, ST_ERR_ARG, "NULL argument");
-            ply_chain(c, fd, h, element, ch);
-        },
-        actions, nactions, iters, draws, ndraws, used, dos_time, dos_date, out, out_size, nullptr, nullptr);
+    return guard([&] {
+        sog_chain(
+            c, [&](Chain &ch) {
+                ST_ARG(c && h && fd >= 0, "NULL argument");
+                ply_chain(c, fd, h, element, ch);
+            },
+            actions, nactions, iters, draws, ndraws, used, SogSink::buffer(out, out_size, dos_time, dos_date));
+    });
 }
 
 int st_sog_bundle_process(st_ctx *c, const st_ttable *src, const st_action *actions, int32_t nactions, int32_t iters,
                           const double *draws, uint64_t ndraws, uint64_t *used, uint16_t dos_time, uint16_t dos_date,
                           uint8_t **out, uint64_t *out_size) {
-    return sog_chain(
-        c, [&](Chain &ch) {
-            ST_REQUIRE(c && src, ST_ERR_ARG, "NULL argument");
-            check_src(src);
-            upload_chain(c, src, ch);
-        },
-        actions, nactions, iters, draws, ndraws, used, dos_time, dos_date, out, out_size, nullptr, nullptr);
+    return guard([&] {
+        sog_chain(c, host_loader(c, src), actions, nactions, iters, draws, ndraws, used,
+                  SogSink::buffer(out, out_size, dos_time, dos_date));
+    });
 }
 
 int st_sog_process(st_ctx *c, const st_ttable *src, const st_action *actions, int32_t nactions, int32_t iters,
                    const double *draws, uint64_t ndraws, uint64_t *used, st_sog_meta *meta,
                    const st_sog_textures *out) {
-    ST_REQUIRE_RC(meta && out, "NULL argument");
-    return sog_chain(
-        c, [&](Chain &ch) {
-            ST_REQUIRE(c && src, ST_ERR_ARG, "NULL argument");
-            check_src(src);
-            upload_chain(c, src, ch);
-        },
-        actions, nactions, iters, draws, ndraws, used, 0, 0, nullptr, nullptr, meta, out);
+    return guard([&] {
+        sog_chain(c, host_loader(c, src), actions, nactions, iters, draws, ndraws, used, SogSink::textures(meta, out));
+    });
 }
 
 int st_dev_sog_t(st_ctx *c, const st_ttable *t, int32_t iters, const double *draws, uint64_t ndraws, uint64_t *used,

@@ -29,10 +29,6 @@ struct Batch {
     st_ctx *c;
     std::vector<HostXfer> v;
     template <typename T>
-    void add(const T *host, T *dev, size_t count) {
-        v.push_back(HostXfer{const_cast<T *>(host), dev, count * sizeof(T)});
-    }
-    template <typename T>
     void add_d2h(T *host, const T *dev, size_t count) {
         v.push_back(HostXfer{host, const_cast<T *>(dev), count * sizeof(T)});
     }
@@ -60,9 +56,8 @@ DevTable upload(st_ctx *c, const st_table *h, const std::vector<std::string> &wa
     Batch up{c};
     for (size_t i = 0; i < d.names.size(); ++i) {
         const int src = find_col(h, d.names[i].c_str());
-        float *p = wsT<float>(c, tag + std::to_string(i), h->n);
-        up.add(h->cols[src], p, h->n);
-        d.cols.push_back(p);
+        d.cols.push_back(static_cast<float *>(
+            ws_upload(c, tag + std::to_string(i), h->cols[src], h->n * sizeof(float), up.v)));
     }
     up.h2d();
     for (auto &s : d.names) d.cnames.push_back(s.c_str());
@@ -80,15 +75,6 @@ void download(st_ctx *c, const DevTable &d, const st_table *h) {
         down.add_d2h(h->cols[dst], d.cols[i], h->n);
     }
     down.d2h();
-}
-
-// the columns writeSog reads (write-sog.ts:110-370): the other columns of a PLY (normals, extra
-// properties) are not uploaded
-std::vector<std::string> sog_columns() {
-    std::vector<std::string> v = {"x", "y", "z", "scale_0", "scale_1", "scale_2", "f_dc_0",
-                                  "f_dc_1", "f_dc_2", "opacity", "rot_0", "rot_1", "rot_2", "rot_3"};
-    for (int i = 0; i < 45; ++i) v.push_back("f_rest_" + std::to_string(i));
-    return v;
 }
 
 std::vector<std::string> transform_columns() {
@@ -184,9 +170,8 @@ bool resident_table(st_ctx *c, const st_table *h, const std::vector<std::string>
         d.names.push_back(h->names[src[j]]);
         const auto &m = ms[j];
         if (!m.host) {
-            float *p = wsT<float>(c, tag + std::to_string(j), h->n);
-            up.v.push_back(HostXfer{static_cast<void *>(h->cols[src[j]]), p, h->n * sizeof(float)});
-            d.cols.push_back(p);
+            d.cols.push_back(static_cast<float *>(
+                ws_upload(c, tag + std::to_string(j), h->cols[src[j]], h->n * sizeof(float), up.v)));
             continue;
         }
         d.cols.push_back(static_cast<float *>(const_cast<void *>(m.dev)));
@@ -278,37 +263,123 @@ void run_host_sog(st_ctx *c, const st_table *t, const std::vector<std::string> &
 // a workspace slot that receives `count` host elements with the batch's next h2d()
 template <typename T>
 T *to_dev(Batch &b, const std::string &slot, const T *h, size_t count) {
-    T *d = wsT<T>(b.c, slot, count);
-    b.add(h, d, count);
-    return d;
+    return static_cast<T *>(ws_upload(b.c, slot, h, count * sizeof(T), b.v));
+}
+
+// the seven textures to the caller's host pointers (the shN pair when the table has bands)
+void textures_to_host(st_ctx *c, const st_sog_textures &dt, const st_sog_meta &meta, const st_sog_textures *out) {
+    const uint64_t tex = (uint64_t)meta.width * meta.height * 4;
+    std::vector<HostXfer> down;
+    for (auto pr : {std::make_pair(out->means_l, dt.means_l), std::make_pair(out->means_u, dt.means_u),
+                    std::make_pair(out->quats, dt.quats), std::make_pair(out->scales, dt.scales),
+                    std::make_pair(out->sh0, dt.sh0)}) {
+        ST_ARG(pr.first, "sog: texture output is NULL");
+        down.push_back(HostXfer{pr.first, pr.second, tex});
+    }
+    if (meta.sh_bands > 0) {
+        ST_ARG(out->shn_labels && out->shn_centroids, "sog: shN outputs are NULL");
+        down.push_back(HostXfer{out->shn_labels, dt.shn_labels, tex});
+        down.push_back(HostXfer{out->shn_centroids, dt.shn_centroids, (uint64_t)meta.shn_width * meta.shn_height * 4});
+    }
+    staged_d2h(c, down);
+}
+
+// an archive view (sog_bundle_dev's pinned buffer) copied into a malloc'd buffer (st_free)
+uint8_t *archive_malloc(const uint8_t *view, uint64_t nb) {
+    uint8_t *buf = (uint8_t *)std::malloc(nb);
+    ST_REQUIRE(buf, ST_ERR_NOMEM, "sog bundle: host allocation failed");
+    std::memcpy(buf, view, nb);
+    return buf;
+}
+
+// writeSog of a host table into the sink: sharded over the default group when there is one, else
+// on c, from the columns resident in HBM where it can (run_host_sog).  A file takes the archive
+// streamed beside the step (sog_file_dev); its descriptor is checked before any group work.
+void host_sog(st_ctx *c, const st_table *t, int iters, const double *draws, uint64_t ndraws, uint64_t *used,
+              const SogSink &to) {
+    const bool file = to.kind == SogSink::TO_FILE;
+    const char *bad = file ? "bad argument" : "NULL argument";
+    if (const auto g = sog_group()) {  // held for the whole call
+        if (file) {
+            ST_ARG(to.size, bad);
+            sog_file_check(to.fd);
+        }
+        return group_sog_to(g.get(), &t, 1, nullptr, nullptr, nullptr, iters, draws, ndraws, used, to);
+    }
+    ST_ARG(c && t && to.ok(), bad);
+    use_device(c);
+    if (file) sog_file_check(to.fd);
+    const st_sog_textures dt = sog_textures(c, t->n, sh_coeffs_of(t));
+    st_sog_meta meta{};
+    uint64_t u = 0;
+    run_host_sog(c, t, sog_columns(), "h.s", [&](const st_table *dtab) {
+        if (file) {
+            u = sog_file_dev(c, dtab, iters, draws, ndraws, &meta, &dt, to.fd, to.dos_time, to.dos_date, to.size);
+            return;
+        }
+        u = sog_dev(c, dtab, iters, draws, ndraws, &meta, &dt);
+        spec_gate(c);
+    });
+    if (!file) sog_deliver(c, dt, meta, t->n, to);
+    if (used) *used = u;
 }
 
 }  // namespace
+
+const std::vector<std::string> &sog_columns() {
+    static const std::vector<std::string> cols = [] {
+        std::vector<std::string> v = {"x", "y", "z", "scale_0", "scale_1", "scale_2", "f_dc_0",
+                                      "f_dc_1", "f_dc_2", "opacity", "rot_0", "rot_1", "rot_2", "rot_3"};
+        for (int i = 0; i < 45; ++i) v.push_back("f_rest_" + std::to_string(i));
+        return v;
+    }();
+    return cols;
+}
+
+st_sog_textures sog_textures(st_ctx *c, uint64_t n, int C) {
+    int32_t W, H, pal, cw, chh;
+    ST_ARG(st_sog_geometry(n, C, &W, &H, &pal, &cw, &chh) == ST_OK, "sog: empty table");
+    const uint64_t tex = (uint64_t)W * H * 4;
+    st_sog_textures dt{};
+    dt.means_l = wsT<uint8_t>(c, "h.s.ml", tex);
+    dt.means_u = wsT<uint8_t>(c, "h.s.mu", tex);
+    dt.quats = wsT<uint8_t>(c, "h.s.q", tex);
+    dt.scales = wsT<uint8_t>(c, "h.s.sc", tex);
+    dt.sh0 = wsT<uint8_t>(c, "h.s.sh0", tex);
+    if (C) {
+        dt.shn_labels = wsT<uint8_t>(c, "h.s.shl", tex);
+        dt.shn_centroids = wsT<uint8_t>(c, "h.s.shc", (uint64_t)cw * chh * 4);
+    }
+    return dt;
+}
+
+void sog_deliver(st_ctx *c, const st_sog_textures &dt, const st_sog_meta &meta, uint64_t count, const SogSink &to) {
+    if (to.kind == SogSink::TO_HOST) {
+        textures_to_host(c, dt, meta, to.tex);
+        *to.meta = meta;
+        return;
+    }
+    const uint8_t *view;
+    uint64_t nb;
+    sog_bundle_dev(c, meta, count, dt, to.dos_time, to.dos_date, &view, &nb);
+    if (to.kind == SogSink::TO_FILE) {  // as sog_file_dev leaves the file: written from offset 0, then cut
+        write_at(to.fd, view, nb, 0);
+        sog_file_truncate(to.fd, nb);
+    } else {
+        *to.out = archive_malloc(view, nb);
+    }
+    *to.size = nb;
+}
+
 }  // namespace st
 
 using namespace st;
 
-template <typename F>
-static int guarded_h(F &&f) {
-    try {
-        f();
-        return ST_OK;
-    } catch (const st::Error &e) {
-        set_last_error(e.what());
-        return e.code;
-    } catch (const std::exception &e) {
-        set_last_error(e.what());
-        return ST_ERR_INTERNAL;
-    }
-}
-
-#define ST_ARGH(cond, msg) ST_REQUIRE(cond, ST_ERR_ARG, msg)
-
 extern "C" {
 
 int st_transform(st_ctx *c, const st_table *t, const st_transform_params *p) {
-    return guarded_h([&] {
-        ST_ARGH(c && t && p, "NULL argument");
+    return guard([&] {
+        ST_ARG(c && t && p, "NULL argument");
         use_device(c);
         DevTable d = upload(c, t, transform_columns(), "h.t");
         transform_dev(c, &d.t, p);
@@ -319,8 +390,8 @@ int st_transform(st_ctx *c, const st_table *t, const st_transform_params *p) {
 // transform() on a typed host table, in place: the transformed columns (x y z rot_* scale_*
 // f_rest_*, any type) go up, through the typed kernel, and back
 int st_transform_t(st_ctx *c, const st_ttable *t, const st_transform_params *p) {
-    return guarded_h([&] {
-        ST_ARGH(c && t && p && (t->ncol == 0 || (t->names && t->types && t->cols)), "NULL argument");
+    return guard([&] {
+        ST_ARG(c && t && p && (t->ncol == 0 || (t->names && t->types && t->cols)), "NULL argument");
         use_device(c);
         const auto want = transform_columns();
         std::vector<const char *> names;
@@ -333,9 +404,8 @@ int st_transform_t(st_ctx *c, const st_ttable *t, const st_transform_params *p) 
             for (auto &w : want) hit = hit || (w == t->names[i]);
             if (!hit) continue;
             const int sz = type_size(t->types[i]);
-            ST_ARGH(sz > 0 && (t->cols[i] || t->n == 0), "transform: bad column");
-            void *d = ws(c, "h.tt" + std::to_string(i), t->n * sz + 16);
-            b.add(static_cast<const char *>(t->cols[i]), static_cast<char *>(d), t->n * sz);
+            ST_ARG(sz > 0 && (t->cols[i] || t->n == 0), "transform: bad column");
+            void *d = ws_upload(c, "h.tt" + std::to_string(i), t->cols[i], t->n * sz, b.v);
             names.push_back(t->names[i]);
             types.push_back(t->types[i]);
             dcols.push_back(d);
@@ -353,18 +423,16 @@ int st_transform_t(st_ctx *c, const st_ttable *t, const st_transform_params *p) 
 
 // generateOrdering of x / y / z columns of any types (ST_PLY_*)
 int st_morton_order_t(st_ctx *c, const void *const xyz[3], const int32_t types[3], uint32_t *idx, uint64_t n) {
-    return guarded_h([&] {
-        ST_ARGH(c && xyz && types && ((xyz[0] && xyz[1] && xyz[2] && idx) || n == 0), "NULL argument");
+    return guard([&] {
+        ST_ARG(c && xyz && types && ((xyz[0] && xyz[1] && xyz[2] && idx) || n == 0), "NULL argument");
         if (n == 0) return;
         use_device(c);
         Batch b{c};
         const void *d[3];
         for (int a = 0; a < 3; ++a) {
             const int sz = type_size(types[a]);
-            ST_ARGH(sz > 0, "morton: bad column type");
-            char *p = static_cast<char *>(ws(c, "h.mt" + std::to_string(a), n * sz + 16));
-            b.add(static_cast<const char *>(xyz[a]), p, n * sz);
-            d[a] = p;
+            ST_ARG(sz > 0, "morton: bad column type");
+            d[a] = ws_upload(c, "h.mt" + std::to_string(a), xyz[a], n * sz, b.v);
         }
         uint32_t *di = to_dev(b, "h.mi", idx, n);
         b.h2d();
@@ -375,8 +443,8 @@ int st_morton_order_t(st_ctx *c, const void *const xyz[3], const int32_t types[3
 }
 
 int st_filter_finite(st_ctx *c, const st_table *t, uint32_t *out_idx, uint64_t *out_n) {
-    return guarded_h([&] {
-        ST_ARGH(c && t && out_idx && out_n, "NULL argument");
+    return guard([&] {
+        ST_ARG(c && t && out_idx && out_n, "NULL argument");
         use_device(c);
         DevTable d = upload(c, t, {}, "h.f");
         auto *didx = wsT<uint32_t>(c, "h.fidx", t->n);
@@ -389,18 +457,17 @@ int st_filter_finite(st_ctx *c, const st_table *t, uint32_t *out_idx, uint64_t *
 }
 
 int st_filter_nan(st_ctx *c, const st_ttable *src, const st_ttable *dst, uint64_t *out_m) {
-    return guarded_h([&] {
-        ST_ARGH(c && src && dst && out_m, "NULL argument");
-        ST_ARGH(src->ncol == dst->ncol && dst->n >= src->n, "filter_nan: dst needs src's columns and n rows");
+    return guard([&] {
+        ST_ARG(c && src && dst && out_m, "NULL argument");
+        ST_ARG(src->ncol == dst->ncol && dst->n >= src->n, "filter_nan: dst needs src's columns and n rows");
         use_device(c);
         const uint64_t n = src->n;
         std::vector<void *> dcols(src->ncol), ocols(src->ncol);
         Batch b{c};
         for (int i = 0; i < src->ncol; ++i) {
             const int sz = type_size(src->types[i]);
-            ST_ARGH(sz > 0 && dst->types[i] == src->types[i], "filter_nan: bad or mismatched column type");
-            dcols[i] = ws(c, "h.fn" + std::to_string(i), n * sz + 16);
-            b.add(static_cast<const char *>(src->cols[i]), static_cast<char *>(dcols[i]), n * sz);
+            ST_ARG(sz > 0 && dst->types[i] == src->types[i], "filter_nan: bad or mismatched column type");
+            dcols[i] = ws_upload(c, "h.fn" + std::to_string(i), src->cols[i], n * sz, b.v);
         }
         b.h2d();
         st_ttable d = *src;
@@ -421,8 +488,8 @@ int st_filter_nan(st_ctx *c, const st_ttable *src, const st_ttable *dst, uint64_
 }
 
 int st_morton_order(st_ctx *c, const float *x, const float *y, const float *z, uint32_t *idx, uint64_t n) {
-    return guarded_h([&] {
-        ST_ARGH(c && ((x && y && z && idx) || n == 0), "NULL argument");
+    return guard([&] {
+        ST_ARG(c && ((x && y && z && idx) || n == 0), "NULL argument");
         if (n == 0) return;
         use_device(c);
         Batch b{c};
@@ -437,8 +504,8 @@ int st_morton_order(st_ctx *c, const float *x, const float *y, const float *z, u
 
 int st_pack_compressed(st_ctx *c, const st_table *t, const uint32_t *order, float *chunk, uint32_t *vertex,
                        uint8_t *sh) {
-    return guarded_h([&] {
-        ST_ARGH(c && t && ((order && chunk && vertex) || t->n == 0), "NULL argument");
+    return guard([&] {
+        ST_ARG(c && t && ((order && chunk && vertex) || t->n == 0), "NULL argument");
         if (t->n == 0) return;
         use_device(c);
         DevTable d = upload(c, t, {}, "h.c");
@@ -460,8 +527,8 @@ int st_pack_compressed(st_ctx *c, const st_table *t, const uint32_t *order, floa
 
 int st_kmeans(st_ctx *c, const float *const *cols, int32_t d, uint64_t n, int32_t k, int32_t iters,
               const double *draws, uint64_t ndraws, uint64_t *used, float *centroids, uint32_t *labels) {
-    return guarded_h([&] {
-        ST_ARGH(c && cols && d > 0 && k > 0 && centroids && labels, "bad argument");
+    return guard([&] {
+        ST_ARG(c && cols && d > 0 && k > 0 && centroids && labels, "bad argument");
         use_device(c);
         std::vector<const float *> dc(d);
         Batch b{c};
@@ -480,8 +547,8 @@ int st_kmeans(st_ctx *c, const float *const *cols, int32_t d, uint64_t n, int32_
 
 int st_cluster1d(st_ctx *c, const float *const *cols, int32_t ncols, uint64_t n, int32_t iters, const double *draws,
                  uint64_t ndraws, uint64_t *used, float *centroids256, uint8_t *labels) {
-    return guarded_h([&] {
-        ST_ARGH(c && cols && ncols > 0 && centroids256 && labels, "bad argument");
+    return guard([&] {
+        ST_ARG(c && cols && ncols > 0 && centroids256 && labels, "bad argument");
         use_device(c);
         std::vector<const float *> dc(ncols);
         Batch b{c};
@@ -499,135 +566,19 @@ int st_cluster1d(st_ctx *c, const float *const *cols, int32_t ncols, uint64_t n,
 
 int st_sog(st_ctx *c, const st_table *t, int32_t iters, const double *draws, uint64_t ndraws, uint64_t *used,
            st_sog_meta *meta, const st_sog_textures *out) {
-    if (int rc = apply_env_devices()) return rc;
-    if (auto g = default_group()) return st_group_sog(g.get(), &t, 1, nullptr, iters, draws, ndraws, used, meta, out);
-    return guarded_h([&] {
-        ST_ARGH(c && t && meta && out, "NULL argument");
-        use_device(c);
-        const int C = sh_coeffs_of(t);
-        int32_t W, H, pal, cw, chh;
-        ST_REQUIRE(st_sog_geometry(t->n, C, &W, &H, &pal, &cw, &chh) == ST_OK, ST_ERR_ARG, "sog: empty table");
-        const uint64_t tex = (uint64_t)W * H * 4;
-        st_sog_textures dt{};
-        dt.means_l = wsT<uint8_t>(c, "h.s.ml", tex);
-        dt.means_u = wsT<uint8_t>(c, "h.s.mu", tex);
-        dt.quats = wsT<uint8_t>(c, "h.s.q", tex);
-        dt.scales = wsT<uint8_t>(c, "h.s.sc", tex);
-        dt.sh0 = wsT<uint8_t>(c, "h.s.sh0", tex);
-        if (C) {
-            dt.shn_labels = wsT<uint8_t>(c, "h.s.shl", tex);
-            dt.shn_centroids = wsT<uint8_t>(c, "h.s.shc", (uint64_t)cw * chh * 4);
-        }
-        uint64_t u = 0;
-        run_host_sog(c, t, sog_columns(), "h.s", [&](const st_table *dtab) {
-            u = sog_dev(c, dtab, iters, draws, ndraws, meta, &dt);
-            spec_gate(c);
-        });
-        Batch b{c};
-        b.add_d2h(out->means_l, dt.means_l, tex);
-        b.add_d2h(out->means_u, dt.means_u, tex);
-        b.add_d2h(out->quats, dt.quats, tex);
-        b.add_d2h(out->scales, dt.scales, tex);
-        b.add_d2h(out->sh0, dt.sh0, tex);
-        if (C) {
-            ST_ARGH(out->shn_labels && out->shn_centroids, "sog: shN outputs are NULL");
-            b.add_d2h(out->shn_labels, dt.shn_labels, tex);
-            b.add_d2h(out->shn_centroids, dt.shn_centroids, (uint64_t)cw * chh * 4);
-        }
-        b.d2h();
-        if (used) *used = u;
-    });
+    return guard([&] { host_sog(c, t, iters, draws, ndraws, used, SogSink::textures(meta, out)); });
 }
 
 // writeSog to a .sog bundle (write-sog.ts:110-370 with the ZipWriter of :112-114):
 // the archive bytes, malloc'd (st_free)
 int st_sog_bundle(st_ctx *c, const st_table *t, int32_t iters, const double *draws, uint64_t ndraws, uint64_t *used,
                   uint16_t dos_time, uint16_t dos_date, uint8_t **out, uint64_t *out_size) {
-    if (int rc = apply_env_devices()) return rc;
-    if (auto g = default_group())
-        return st_group_sog_bundle(g.get(), &t, 1, nullptr, iters, draws, ndraws, used, dos_time, dos_date, out, out_size);
-    return guarded_h([&] {
-        ST_ARGH(c && t && out && out_size, "NULL argument");
-        use_device(c);
-        const int C = sh_coeffs_of(t);
-        int32_t W, H, pal, cw, chh;
-        ST_REQUIRE(st_sog_geometry(t->n, C, &W, &H, &pal, &cw, &chh) == ST_OK, ST_ERR_ARG, "sog: empty table");
-        const uint64_t tex = (uint64_t)W * H * 4;
-        st_sog_textures dt{};
-        dt.means_l = wsT<uint8_t>(c, "h.s.ml", tex);
-        dt.means_u = wsT<uint8_t>(c, "h.s.mu", tex);
-        dt.quats = wsT<uint8_t>(c, "h.s.q", tex);
-        dt.scales = wsT<uint8_t>(c, "h.s.sc", tex);
-        dt.sh0 = wsT<uint8_t>(c, "h.s.sh0", tex);
-        if (C) {
-            dt.shn_labels = wsT<uint8_t>(c, "h.s.shl", tex);
-            dt.shn_centroids = wsT<uint8_t>(c, "h.s.shc", (uint64_t)cw * chh * 4);
-        }
-        st_sog_meta meta{};
-        uint64_t u = 0;
-        run_host_sog(c, t, sog_columns(), "h.s", [&](const st_table *dtab) {
-            u = sog_dev(c, dtab, iters, draws, ndraws, &meta, &dt);
-            spec_gate(c);
-        });
-        const uint8_t *view;
-        uint64_t nb;
-        sog_bundle_dev(c, meta, t->n, dt, dos_time, dos_date, &view, &nb);
-        uint8_t *buf = (uint8_t *)std::malloc(nb);
-        ST_REQUIRE(buf, ST_ERR_NOMEM, "sog bundle: host allocation failed");
-        std::memcpy(buf, view, nb);
-        *out = buf;
-        *out_size = nb;
-        if (used) *used = u;
-    });
+    return guard([&] { host_sog(c, t, iters, draws, ndraws, used, SogSink::buffer(out, out_size, dos_time, dos_date)); });
 }
 
 int st_sog_file(st_ctx *c, const st_table *t, int32_t iters, const double *draws, uint64_t ndraws, uint64_t *used,
                 int32_t fd, uint16_t dos_time, uint16_t dos_date, uint64_t *size) {
-    if (int rc = apply_env_devices()) return rc;
-    if (auto g = default_group()) {  // rows sharded over GPUs: the group's archive, then one write
-        if (int rc = guarded_h([&] {
-                ST_ARGH(size, "bad argument");
-                sog_file_check(fd);
-            }))
-            return rc;
-        uint8_t *zip = nullptr;
-        uint64_t nb = 0;
-        if (int rc = st_group_sog_bundle(g.get(), &t, 1, nullptr, iters, draws, ndraws, used, dos_time, dos_date, &zip,
-                                         &nb))
-            return rc;
-        const int rc = guarded_h([&] {  // the same writer as the one-GPU path: from offset 0, then truncated
-            write_at(fd, zip, nb, 0);
-            sog_file_truncate(fd, nb);
-            *size = nb;
-        });
-        std::free(zip);
-        return rc;
-    }
-    return guarded_h([&] {
-        ST_ARGH(c && t && size && fd >= 0, "bad argument");
-        use_device(c);
-        sog_file_check(fd);
-        const int C = sh_coeffs_of(t);
-        int32_t W, H, pal, cw, chh;
-        ST_REQUIRE(st_sog_geometry(t->n, C, &W, &H, &pal, &cw, &chh) == ST_OK, ST_ERR_ARG, "sog: empty table");
-        const uint64_t tex = (uint64_t)W * H * 4;
-        st_sog_textures dt{};
-        dt.means_l = wsT<uint8_t>(c, "h.s.ml", tex);
-        dt.means_u = wsT<uint8_t>(c, "h.s.mu", tex);
-        dt.quats = wsT<uint8_t>(c, "h.s.q", tex);
-        dt.scales = wsT<uint8_t>(c, "h.s.sc", tex);
-        dt.sh0 = wsT<uint8_t>(c, "h.s.sh0", tex);
-        if (C) {
-            dt.shn_labels = wsT<uint8_t>(c, "h.s.shl", tex);
-            dt.shn_centroids = wsT<uint8_t>(c, "h.s.shc", (uint64_t)cw * chh * 4);
-        }
-        st_sog_meta meta{};
-        uint64_t u = 0;
-        run_host_sog(c, t, sog_columns(), "h.s", [&](const st_table *dtab) {
-            u = sog_file_dev(c, dtab, iters, draws, ndraws, &meta, &dt, fd, dos_time, dos_date, size);
-        });
-        if (used) *used = u;
-    });
+    return guard([&] { host_sog(c, t, iters, draws, ndraws, used, SogSink::file(fd, size, dos_time, dos_date)); });
 }
 
 }  // extern "C"

@@ -54,6 +54,7 @@ extern bool g_sync_check;
     do {                                             \
         if (!(cond)) throw ::st::Error((code), (msg)); \
     } while (0)
+#define ST_ARG(cond, msg) ST_REQUIRE(cond, ST_ERR_ARG, msg)
 
 // runs f at the extern "C" boundary: st::Error -> its code + st_last_error()
 template <typename F>
@@ -228,6 +229,12 @@ struct HostXfer {
 };
 void staged_h2d(st_ctx *c, const std::vector<HostXfer> &xs);
 void staged_d2h(st_ctx *c, const std::vector<HostXfer> &xs);
+// a workspace slot (16 bytes of padding) that receives `bytes` of host memory with xs' staged_h2d
+inline void *ws_upload(st_ctx *c, const std::string &slot, const void *host, size_t bytes, std::vector<HostXfer> &xs) {
+    void *d = ws(c, slot, bytes + 16);
+    xs.push_back(HostXfer{const_cast<void *>(host), d, bytes});
+    return d;
+}
 void staged_h2d_raw(st_ctx *c, const std::vector<HostXfer> &xs);  // without the mirrors' bookkeeping
 void staged_d2h_raw(st_ctx *c, const std::vector<HostXfer> &xs);  // without the mirrors' bookkeeping
 // st_ctx::HostMirror bookkeeping of the staged copies (st_ply.hip): lazy sources are copied down
@@ -301,7 +308,10 @@ void iota_u32(st_ctx *c, uint32_t *out, uint64_t n);
 // column lookups on an st_table
 int find_col(const st_table *t, const char *name);
 float *col_or_null(const st_table *t, const char *name);
-int sh_coeffs_of(const st_table *t);  // band rule: transform.ts:20 / write-sog.ts:296
+// band rule (transform.ts:20 / write-sog.ts:296): the SH coefficients per channel from the first
+// f_rest_i that `has` does not find -- { '9': 1, '24': 2, '-1': 3 }[index] ?? 0 bands: 3, 8, 15 or 0
+int band_coeffs(const std::function<bool(const char *)> &has);
+int sh_coeffs_of(const st_table *t);  // of one table's columns
 
 // module entry points (device pointers)
 void transform_dev(st_ctx *c, const st_table *t, const st_transform_params *p);
@@ -428,9 +438,9 @@ struct ProcessedF32 {
 void chain_apply_f32(st_ctx *c, const st_table *in, const st_action *actions, int nactions, const std::string &tag,
                      ProcessedF32 &out);
 
-// multi-GPU writeSog (st_multi.hip): the st_set_devices group (empty: one device); the returned
+// multi-GPU writeSog (st_multi.hip): the st_set_devices group a one-call form shards its rows over
+// (ST_NUM_GPUS applied on first use; its error is thrown), empty: one device.  The returned
 // reference keeps the group alive for the caller's call even if st_set_devices replaces it
-std::shared_ptr<st_group> default_group();
-int apply_env_devices();  // ST_NUM_GPUS on first use; ST_OK or the error (st_last_error set)
+std::shared_ptr<st_group> sog_group();
 
 }  // namespace st

@@ -600,8 +600,6 @@ __global__ __launch_bounds__(256) void k_scatter_back(const uint32_t *__restrict
 
 
 
-__global__ void k_set_sentinel(uint32_t *a, uint32_t i, uint32_t v) { a[i] = v; }
-
 // Runs of equal keys longer than 256 (ordering.ts:90-104) without listing every run: j
 // starts such a run iff it starts a run and keys[j + 256] == keys[j] (the keys are sorted).
 // Their order in the next level's segment list is immaterial: a segment's rows go back to

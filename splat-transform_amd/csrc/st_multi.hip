@@ -1216,20 +1216,6 @@ std::shared_ptr<st_group> g_group;  // st_set_devices (a caller holds its own re
 int g_ndev = 1;
 std::atomic<bool> g_env_done{false};  // ST_NUM_GPUS applied (or overridden by st_set_devices)
 
-template <typename F>
-int guarded_m(F &&f) {
-    try {
-        f();
-        return ST_OK;
-    } catch (const st::Error &e) {
-        set_last_error(e.what());
-        return e.code;
-    } catch (const std::exception &e) {
-        set_last_error(e.what());
-        return ST_ERR_INTERNAL;
-    }
-}
-
 st_group *group_new(const int32_t *devices, int n, bool host_staged) {
     auto g = std::make_unique<st_group>();
     for (int r = 0; r < n; ++r) {
@@ -1277,12 +1263,11 @@ RankSlice upload_slice(st_ctx *c, const st_table *const *tabs, int ntab, uint64_
 }
 }  // namespace
 
-// the group form of writeSog from host tables; textures on rank 0's device (dev_out) and,
-// if host_out, copied there
+// the group form of writeSog from host tables: the textures on rank 0's device (dev_out), *n_out
+// rows (after the actions, when given); returns the draws used
 static uint64_t group_sog(st_group *g, const st_table *const *tabs, int ntab, const uint64_t *splits, int iters,
                           const double *draws, uint64_t ndraws, st_sog_meta *meta, const st_sog_textures *dev_out,
-                          const st_action *const *actions = nullptr, const int32_t *nactions = nullptr,
-                          uint64_t *n_out = nullptr) {
+                          const st_action *const *actions, const int32_t *nactions, uint64_t *n_out) {
     uint64_t N = 0;
     for (int t = 0; t < ntab; ++t) N += tabs[t]->n;
     const int world = (int)g->ctx.size();
@@ -1313,44 +1298,37 @@ static uint64_t group_sog(st_group *g, const st_table *const *tabs, int ntab, co
     return used[0];
 }
 
-struct GroupTex {
-    st_sog_textures t{};
-};
+namespace st {
+int apply_env_devices();  // ST_NUM_GPUS on first use; ST_OK or the error (st_last_error set)
 
-static GroupTex group_tex(st_ctx *c, uint64_t N, int C) {
-    int32_t W, H, pal, cw, chh;
-    st_sog_geometry(N, C, &W, &H, &pal, &cw, &chh);
-    const uint64_t tex = (uint64_t)W * H * 4;
-    GroupTex g;
-    g.t.means_l = wsT<uint8_t>(c, "gs.ml", tex);
-    g.t.means_u = wsT<uint8_t>(c, "gs.mu", tex);
-    g.t.quats = wsT<uint8_t>(c, "gs.q", tex);
-    g.t.scales = wsT<uint8_t>(c, "gs.sc", tex);
-    g.t.sh0 = wsT<uint8_t>(c, "gs.sh0", tex);
-    if (C) {
-        g.t.shn_labels = wsT<uint8_t>(c, "gs.shl", tex);
-        g.t.shn_centroids = wsT<uint8_t>(c, "gs.shc", (uint64_t)cw * chh * 4);
-    }
-    return g;
-}
-
-// band of the combined tables (union of names, write-sog.ts:296)
-static int union_coeffs(const st_table *const *tabs, int ntab) {
-    int miss = -1;
-    for (int i = 0; i < 45 && miss < 0; ++i) {
-        char nm[32];
-        snprintf(nm, sizeof nm, "f_rest_%d", i);
+void group_sog_to(st_group *g, const st_table *const *tabs, int ntab, const uint64_t *splits,
+                  const st_action *const *actions, const int32_t *nactions, int iters, const double *draws,
+                  uint64_t ndraws, uint64_t *used, const SogSink &to) {
+    ST_ARG(g && tabs && ntab >= 1 && to.ok(), "NULL argument");
+    uint64_t N = 0;
+    for (int t = 0; t < ntab; ++t) N += tabs[t]->n;
+    // the band of the combined tables (union of names, write-sog.ts:296).  With actions: textures for
+    // the unprocessed row count and band 3 -- filters only shrink the table and filterBands only
+    // lowers the band, so these hold the processed table's
+    const int C = actions ? 15 : band_coeffs([&](const char *nm) {
         bool any = false;
         for (int t = 0; t < ntab; ++t) any = any || find_col(tabs[t], nm) >= 0;
-        if (!any) miss = i;
-    }
-    return miss == 9 ? 3 : miss == 24 ? 8 : miss == -1 ? 15 : 0;
+        return any;
+    });
+    st_ctx *c = g->ctx[0];
+    const st_sog_textures dt = sog_textures(c, N, C);
+    st_sog_meta meta{};
+    const uint64_t u = group_sog(g, tabs, ntab, splits, iters, draws, ndraws, &meta, &dt, actions, nactions, &N);
+    use_device(c);
+    sog_deliver(c, dt, meta, N, to);
+    if (used) *used = u;
 }
+}  // namespace st
 
 extern "C" {
 
 int st_comm_unique_id(uint8_t id[128]) {
-    return guarded_m([&] {
+    return guard([&] {
         ST_REQUIRE(id, ST_ERR_ARG, "NULL argument");
         static_assert(sizeof(ncclUniqueId) == 128, "ncclUniqueId size");
         ncclUniqueId u;
@@ -1360,7 +1338,7 @@ int st_comm_unique_id(uint8_t id[128]) {
 }
 
 int st_comm_init_rank(st_ctx *c, int32_t world, int32_t rank, const uint8_t id[128], st_comm **out) {
-    return guarded_m([&] {
+    return guard([&] {
         ST_REQUIRE(c && id && out && world >= 1 && rank >= 0 && rank < world, ST_ERR_ARG, "bad argument");
         use_device(c);
         auto rc = std::make_unique<RcclColl>();
@@ -1377,7 +1355,7 @@ int st_comm_init_rank(st_ctx *c, int32_t world, int32_t rank, const uint8_t id[1
 
 int st_comm_init_host(st_ctx *c, int32_t world, int32_t rank, const char *name, uint64_t slot_bytes,
                       double timeout_s, st_comm **out) {
-    return guarded_m([&] {
+    return guard([&] {
         ST_REQUIRE(c && name && out && world >= 1 && rank >= 0 && rank < world, ST_ERR_ARG, "bad argument");
         use_device(c);
         auto *cm = new st_comm();
@@ -1394,7 +1372,7 @@ int st_comm_init_host(st_ctx *c, int32_t world, int32_t rank, const char *name, 
 void st_comm_destroy(st_comm *cm) { delete cm; }
 
 int st_comm_count(const st_comm *cm, int32_t *count) {
-    return guarded_m([&] {
+    return guard([&] {
         ST_REQUIRE(cm && count, ST_ERR_ARG, "NULL argument");
         const auto *rc = dynamic_cast<const RcclColl *>(cm->coll.get());
         *count = rc ? rc->count() : cm->coll->world;
@@ -1404,7 +1382,7 @@ int st_comm_count(const st_comm *cm, int32_t *count) {
 int st_dev_sog_sharded(st_ctx *c, st_comm *cm, const st_table *const *locals, int32_t nlocal, int32_t iters,
                        const double *draws, uint64_t ndraws, uint64_t *used, st_sog_meta *meta,
                        const st_sog_textures *out) {
-    return guarded_m([&] {
+    return guard([&] {
         ST_REQUIRE(c && cm && locals && nlocal >= 1 && draws, ST_ERR_ARG, "NULL argument");
         for (int i = 0; i < nlocal; ++i) ST_REQUIRE(locals[i], ST_ERR_ARG, "NULL table");
         if (cm->coll->rank == 0) ST_REQUIRE(meta && out, ST_ERR_ARG, "rank 0 needs meta and outputs");
@@ -1414,7 +1392,7 @@ int st_dev_sog_sharded(st_ctx *c, st_comm *cm, const st_table *const *locals, in
 }
 
 int st_group_create(const int32_t *devices, int32_t n, int32_t host_staged, st_group **out) {
-    return guarded_m([&] {
+    return guard([&] {
         ST_REQUIRE(devices && n >= 1 && out, ST_ERR_ARG, "bad argument");
         *out = group_new(devices, n, host_staged != 0);
     });
@@ -1425,54 +1403,18 @@ void st_group_destroy(st_group *g) { delete g; }
 int st_group_sog(st_group *g, const st_table *const *tables, int32_t ntables, const uint64_t *splits, int32_t iters,
                  const double *draws, uint64_t ndraws, uint64_t *used, st_sog_meta *meta,
                  const st_sog_textures *out) {
-    return guarded_m([&] {
-        ST_REQUIRE(g && tables && ntables >= 1 && meta && out, ST_ERR_ARG, "NULL argument");
-        uint64_t N = 0;
-        for (int t = 0; t < ntables; ++t) N += tables[t]->n;
-        const int C = union_coeffs(tables, ntables);
-        GroupTex dt = group_tex(g->ctx[0], N, C);
-        const uint64_t u = group_sog(g, tables, ntables, splits, iters, draws, ndraws, meta, &dt.t);
-        st_ctx *c = g->ctx[0];
-        use_device(c);
-        const uint64_t tex = (uint64_t)meta->width * meta->height * 4;
-        uint8_t *dst[6] = {out->means_l, out->means_u, out->quats, out->scales, out->sh0, out->shn_labels};
-        uint8_t *src[6] = {dt.t.means_l, dt.t.means_u, dt.t.quats, dt.t.scales, dt.t.sh0, dt.t.shn_labels};
-        std::vector<HostXfer> down;
-        for (int i = 0; i < (C ? 6 : 5); ++i) {
-            ST_REQUIRE(dst[i], ST_ERR_ARG, "sog: texture output is NULL");
-            down.push_back(HostXfer{dst[i], src[i], tex});
-        }
-        if (C) {
-            ST_REQUIRE(out->shn_centroids, ST_ERR_ARG, "sog: shN outputs are NULL");
-            down.push_back(HostXfer{out->shn_centroids, dt.t.shn_centroids,
-                                    (size_t)meta->shn_width * meta->shn_height * 4});
-        }
-        staged_d2h(c, down);
-        if (used) *used = u;
+    return guard([&] {
+        group_sog_to(g, tables, ntables, splits, nullptr, nullptr, iters, draws, ndraws, used,
+                     SogSink::textures(meta, out));
     });
 }
 
 int st_group_sog_bundle(st_group *g, const st_table *const *tables, int32_t ntables, const uint64_t *splits,
                         int32_t iters, const double *draws, uint64_t ndraws, uint64_t *used, uint16_t dos_time,
                         uint16_t dos_date, uint8_t **out, uint64_t *out_size) {
-    return guarded_m([&] {
-        ST_REQUIRE(g && tables && ntables >= 1 && out && out_size, ST_ERR_ARG, "NULL argument");
-        uint64_t N = 0;
-        for (int t = 0; t < ntables; ++t) N += tables[t]->n;
-        GroupTex dt = group_tex(g->ctx[0], N, union_coeffs(tables, ntables));
-        st_sog_meta meta{};
-        const uint64_t u = group_sog(g, tables, ntables, splits, iters, draws, ndraws, &meta, &dt.t);
-        st_ctx *c = g->ctx[0];
-        use_device(c);
-        const uint8_t *view;
-        uint64_t nb;
-        sog_bundle_dev(c, meta, N, dt.t, dos_time, dos_date, &view, &nb);
-        uint8_t *buf = (uint8_t *)std::malloc(nb);
-        ST_REQUIRE(buf, ST_ERR_NOMEM, "sog bundle: host allocation failed");
-        std::memcpy(buf, view, nb);
-        *out = buf;
-        *out_size = nb;
-        if (used) *used = u;
+    return guard([&] {
+        group_sog_to(g, tables, ntables, splits, nullptr, nullptr, iters, draws, ndraws, used,
+                     SogSink::buffer(out, out_size, dos_time, dos_date));
     });
 }
 
@@ -1480,35 +1422,17 @@ int st_group_sog_bundle_process(st_group *g, const st_table *const *tables, int3
                                 const st_action *const *actions, const int32_t *nactions, int32_t iters,
                                 const double *draws, uint64_t ndraws, uint64_t *used, uint16_t dos_time,
                                 uint16_t dos_date, uint8_t **out, uint64_t *out_size) {
-    return guarded_m([&] {
-        ST_REQUIRE(g && tables && ntables >= 1 && out && out_size && actions && nactions, ST_ERR_ARG, "NULL argument");
-        for (int t = 0; t < ntables; ++t) ST_REQUIRE(nactions[t] == 0 || actions[t], ST_ERR_ARG, "NULL action list");
-        uint64_t N0 = 0;
-        for (int t = 0; t < ntables; ++t) N0 += tables[t]->n;
-        // textures for the unprocessed row count and band: filters only shrink the table and
-        // filterBands only lowers the band, so these hold the processed table's
-        GroupTex dt = group_tex(g->ctx[0], N0, 15);
-        st_sog_meta meta{};
-        uint64_t N = 0;
-        const uint64_t u = group_sog(g, tables, ntables, splits, iters, draws, ndraws, &meta, &dt.t, actions, nactions,
-                                     &N);
-        st_ctx *c = g->ctx[0];
-        use_device(c);
-        const uint8_t *view;
-        uint64_t nb;
-        sog_bundle_dev(c, meta, N, dt.t, dos_time, dos_date, &view, &nb);
-        uint8_t *buf = (uint8_t *)std::malloc(nb);
-        ST_REQUIRE(buf, ST_ERR_NOMEM, "sog bundle: host allocation failed");
-        std::memcpy(buf, view, nb);
-        *out = buf;
-        *out_size = nb;
-        if (used) *used = u;
+    return guard([&] {
+        ST_ARG(g && tables && ntables >= 1 && out && out_size && actions && nactions, "NULL argument");
+        for (int t = 0; t < ntables; ++t) ST_ARG(nactions[t] == 0 || actions[t], "NULL action list");
+        group_sog_to(g, tables, ntables, splits, actions, nactions, iters, draws, ndraws, used,
+                     SogSink::buffer(out, out_size, dos_time, dos_date));
     });
 }
 
 int st_set_devices(int32_t ngpu) {
     g_env_done.store(true);  // an explicit choice overrides ST_NUM_GPUS
-    return guarded_m([&] {
+    return guard([&] {
         int avail = 0;
         ST_HIP(hipGetDeviceCount(&avail));
         ST_REQUIRE(ngpu >= 1 && ngpu <= avail, ST_ERR_ARG,
@@ -1527,7 +1451,7 @@ int st_set_devices(int32_t ngpu) {
 
 int st_get_devices(int32_t *ngpu) {
     if (!ngpu) return ST_ERR_ARG;
-    if (int rc = st::apply_env_devices()) return rc;
+    if (int rc = apply_env_devices()) return rc;
     *ngpu = g_ndev;
     return ST_OK;
 }
@@ -1558,7 +1482,7 @@ int apply_env_devices() {
         // writers' multi-GPU branches run on a one-GPU box
         const char *gr = getenv("ST_DEFAULT_GROUP_RANKS");
         if (rc == ST_OK && gr && atoi(gr) > 1) {
-            rc = guarded_m([&] {
+            rc = guard([&] {
                 const int n = std::min(atoi(gr), 16);
                 std::vector<int32_t> devs(n, 0);
                 std::shared_ptr<st_group> fresh(group_new(devs.data(), n, true));
@@ -1572,8 +1496,8 @@ int apply_env_devices() {
     if (rc != ST_OK) set_last_error(msg);
     return rc;
 }
-// the process-wide group of st_set_devices (empty: one device); the caller's copy keeps it alive
-std::shared_ptr<st_group> default_group() {
+std::shared_ptr<st_group> sog_group() {
+    if (const int rc = apply_env_devices()) throw Error(rc, st_last_error());
     std::lock_guard<std::mutex> lk(g_group_mu);
     return g_group;
 }

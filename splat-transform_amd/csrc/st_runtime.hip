@@ -350,16 +350,12 @@ float *col_or_null(const st_table *t, const char *name) {
     return i < 0 ? nullptr : t->cols[i];
 }
 
-int sh_coeffs_of(const st_table *t) {
-    // { '9': 1, '24': 2, '-1': 3 }[index of first missing f_rest_i] ?? 0
+int band_coeffs(const std::function<bool(const char *)> &has) {
     int first_missing = -1;
     char nm[32];
-    for (int i = 0; i < 45; ++i) {
+    for (int i = 0; i < 45 && first_missing < 0; ++i) {
         snprintf(nm, sizeof nm, "f_rest_%d", i);
-        if (find_col(t, nm) < 0) {
-            first_missing = i;
-            break;
-        }
+        if (!has(nm)) first_missing = i;
     }
     switch (first_missing) {
         case 9: return 3;
@@ -369,30 +365,15 @@ int sh_coeffs_of(const st_table *t) {
     }
 }
 
+int sh_coeffs_of(const st_table *t) {
+    return band_coeffs([&](const char *nm) { return find_col(t, nm) >= 0; });
+}
+
 }  // namespace st
 
 // ---------------------------------------------------------------------------
 // extern "C" boundary
 using namespace st;
-
-template <typename F>
-static int guarded(F &&f) {
-    try {
-        f();
-        return ST_OK;
-    } catch (const st::Error &e) {
-        set_last_error(e.what());
-        return e.code;
-    } catch (const std::bad_alloc &) {
-        set_last_error("host allocation failed");
-        return ST_ERR_NOMEM;
-    } catch (const std::exception &e) {
-        set_last_error(e.what());
-        return ST_ERR_INTERNAL;
-    }
-}
-
-#define ST_ARG(cond, msg) ST_REQUIRE(cond, ST_ERR_ARG, msg)
 
 static void check_table(const st_table *t) {
     ST_ARG(t != nullptr, "table is NULL");
@@ -407,7 +388,7 @@ int st_abi_version(void) { return ST_ABI_VERSION; }
 const char *st_last_error(void) { return g_last_error.c_str(); }
 
 int st_device_count(int32_t *count) {
-    return guarded([&] {
+    return guard([&] {
         ST_ARG(count, "count is NULL");
         int n = 0;
         ST_HIP(hipGetDeviceCount(&n));
@@ -416,7 +397,7 @@ int st_device_count(int32_t *count) {
 }
 
 int st_ctx_create(int32_t device, st_ctx **out) {
-    return guarded([&] {
+    return guard([&] {
         ST_ARG(out, "out is NULL");
         int n = 0;
         ST_HIP(hipGetDeviceCount(&n));
@@ -474,7 +455,7 @@ void st_ctx_destroy(st_ctx *c) {
 }
 
 int st_ctx_set_stream(st_ctx *c, void *s) {
-    return guarded([&] {
+    return guard([&] {
         ST_ARG(c, "ctx is NULL");
         use_device(c);
         if (s) {
@@ -494,7 +475,7 @@ int st_ctx_set_stream(st_ctx *c, void *s) {
 }
 
 int st_ctx_synchronize(st_ctx *c) {
-    return guarded([&] {
+    return guard([&] {
         ST_ARG(c, "ctx is NULL");
         use_device(c);
         ST_HIP(hipStreamSynchronize(c->stream));
@@ -505,7 +486,7 @@ const char *st_ctx_last_timings(st_ctx *c) { return c ? c->last_timings.c_str() 
 const char *st_ctx_last_kmeans_stats(st_ctx *c) { return c ? c->last_kn_stats.c_str() : "{}"; }
 
 int st_ctx_last_host_reuse(st_ctx *c, uint64_t *columns, uint64_t *bytes) {
-    return guarded([&] {
+    return guard([&] {
         ST_ARG(c && columns && bytes, "NULL argument");
         *columns = c->last_reuse_cols;
         *bytes = c->last_reuse_bytes;
@@ -513,14 +494,14 @@ int st_ctx_last_host_reuse(st_ctx *c, uint64_t *columns, uint64_t *bytes) {
 }
 
 int st_ctx_set_profiling(st_ctx *c, int32_t enable) {
-    return guarded([&] {
+    return guard([&] {
         ST_ARG(c, "ctx is NULL");
         c->profiling = enable != 0;
     });
 }
 
 int st_ctx_reset_kernel_stats(st_ctx *c) {
-    return guarded([&] {
+    return guard([&] {
         ST_ARG(c, "ctx is NULL");
         use_device(c);
         ST_HIP(hipStreamSynchronize(c->stream));
@@ -533,7 +514,7 @@ int st_ctx_reset_kernel_stats(st_ctx *c) {
 }
 
 int st_ctx_kernel_stats(st_ctx *c, const char *name, double *total_ms, uint64_t *launches) {
-    return guarded([&] {
+    return guard([&] {
         ST_ARG(c && name && total_ms && launches, "NULL argument");
         use_device(c);
         double t = 0;
@@ -552,7 +533,7 @@ int st_ctx_kernel_stats(st_ctx *c, const char *name, double *total_ms, uint64_t 
 }
 
 int st_ctx_set_verify(st_ctx *c, int32_t enable) {
-    return guarded([&] {
+    return guard([&] {
         ST_ARG(c, "ctx is NULL");
         c->verify = enable != 0;
     });
@@ -560,7 +541,7 @@ int st_ctx_set_verify(st_ctx *c, int32_t enable) {
 
 int st_ctx_verify_snapshot(st_ctx *c, float *prev, float *cen, uint32_t *labels, int32_t *d, int32_t *k,
                            uint64_t *n) {
-    return guarded([&] {
+    return guard([&] {
         ST_ARG(c && d && k && n, "NULL argument");
         ST_REQUIRE(c->vf_k > 0, ST_ERR_ARG, "no k-means snapshot (st_ctx_set_verify before the call)");
         use_device(c);
@@ -580,7 +561,7 @@ int st_ctx_verify_snapshot(st_ctx *c, float *prev, float *cen, uint32_t *labels,
 
 // ---- device entry points --------------------------------------------------
 int st_dev_transform(st_ctx *c, const st_table *t, const st_transform_params *p) {
-    return guarded([&] {
+    return guard([&] {
         ST_ARG(c && p, "NULL argument");
         check_table(t);
         use_device(c);
@@ -589,7 +570,7 @@ int st_dev_transform(st_ctx *c, const st_table *t, const st_transform_params *p)
 }
 
 int st_dev_transform_t(st_ctx *c, const st_ttable *t, const st_transform_params *p) {
-    return guarded([&] {
+    return guard([&] {
         ST_REQUIRE(c && t && p && (t->ncol == 0 || (t->names && t->types && t->cols)), ST_ERR_ARG, "NULL argument");
         use_device(c);
         transform_tdev(c, t, p);
@@ -597,7 +578,7 @@ int st_dev_transform_t(st_ctx *c, const st_ttable *t, const st_transform_params 
 }
 
 int st_dev_morton_order_t(st_ctx *c, const void *const xyz[3], const int32_t types[3], uint32_t *idx, uint64_t n) {
-    return guarded([&] {
+    return guard([&] {
         ST_REQUIRE(c && xyz && types && ((xyz[0] && xyz[1] && xyz[2] && idx) || n == 0), ST_ERR_ARG, "NULL argument");
         for (int a = 0; a < 3; ++a) ST_REQUIRE(type_size(types[a]) > 0, ST_ERR_ARG, "morton: bad column type");
         use_device(c);
@@ -606,7 +587,7 @@ int st_dev_morton_order_t(st_ctx *c, const void *const xyz[3], const int32_t typ
 }
 
 int st_dev_filter_finite(st_ctx *c, const st_table *t, uint32_t *out_idx, uint64_t *out_n) {
-    return guarded([&] {
+    return guard([&] {
         ST_ARG(c && out_n, "NULL argument");
         check_table(t);
         use_device(c);
@@ -615,7 +596,7 @@ int st_dev_filter_finite(st_ctx *c, const st_table *t, uint32_t *out_idx, uint64
 }
 
 int st_dev_permute_rows(st_ctx *c, const st_table *src, const uint32_t *idx, uint64_t m, const st_table *dst) {
-    return guarded([&] {
+    return guard([&] {
         ST_ARG(c && (idx || m == 0), "NULL argument");
         check_table(src);
         check_table(dst);
@@ -626,7 +607,7 @@ int st_dev_permute_rows(st_ctx *c, const st_table *src, const uint32_t *idx, uin
 }
 
 int st_dev_concat_rows(st_ctx *c, const st_table *const *srcs, int32_t nsrc, const st_table *dst) {
-    return guarded([&] {
+    return guard([&] {
         ST_ARG(c && srcs && nsrc > 0, "NULL argument");
         for (int i = 0; i < nsrc; ++i) check_table(srcs[i]);
         check_table(dst);
@@ -647,7 +628,7 @@ static void check_ttable(const st_ttable *t) {
 }
 
 int st_dev_filter_finite_t(st_ctx *c, const st_ttable *t, uint32_t *out_idx, uint64_t *out_n) {
-    return guarded([&] {
+    return guard([&] {
         ST_ARG(c && out_n && (out_idx || (t && t->n == 0)), "NULL argument");
         check_ttable(t);
         use_device(c);
@@ -656,7 +637,7 @@ int st_dev_filter_finite_t(st_ctx *c, const st_ttable *t, uint32_t *out_idx, uin
 }
 
 int st_dev_permute_rows_t(st_ctx *c, const st_ttable *src, const uint32_t *idx, uint64_t m, const st_ttable *dst) {
-    return guarded([&] {
+    return guard([&] {
         ST_ARG(c && (idx || m == 0), "NULL argument");
         check_ttable(src);
         check_ttable(dst);
@@ -670,7 +651,7 @@ int st_dev_permute_rows_t(st_ctx *c, const st_ttable *src, const uint32_t *idx, 
 
 int st_combine_layout(const st_ttable *const *srcs, int32_t nsrc, int32_t *col_table, int32_t *col_index,
                       int32_t *ncol) {
-    return guarded([&] {
+    return guard([&] {
         ST_ARG(srcs && nsrc > 0 && ncol, "NULL argument");
         for (int i = 0; i < nsrc; ++i) {
             ST_ARG(srcs[i] && srcs[i]->ncol >= 0 && (srcs[i]->ncol == 0 || (srcs[i]->names && srcs[i]->types)),
@@ -681,7 +662,7 @@ int st_combine_layout(const st_ttable *const *srcs, int32_t nsrc, int32_t *col_t
 }
 
 int st_dev_combine(st_ctx *c, const st_ttable *const *srcs, int32_t nsrc, const st_ttable *dst) {
-    return guarded([&] {
+    return guard([&] {
         ST_ARG(c && srcs && nsrc > 0, "NULL argument");
         for (int i = 0; i < nsrc; ++i) check_ttable(srcs[i]);
         check_ttable(dst);
@@ -691,7 +672,7 @@ int st_dev_combine(st_ctx *c, const st_ttable *const *srcs, int32_t nsrc, const 
 }
 
 int st_dev_morton_order(st_ctx *c, const float *x, const float *y, const float *z, uint32_t *idx, uint64_t n) {
-    return guarded([&] {
+    return guard([&] {
         ST_ARG(c && ((x && y && z && idx) || n == 0), "NULL argument");
         use_device(c);
         morton_order_dev(c, x, y, z, idx, n);
@@ -700,7 +681,7 @@ int st_dev_morton_order(st_ctx *c, const float *x, const float *y, const float *
 
 int st_dev_pack_compressed(st_ctx *c, const st_table *t, const uint32_t *order, float *chunk, uint32_t *vertex,
                            uint8_t *sh) {
-    return guarded([&] {
+    return guard([&] {
         ST_ARG(c && ((order && chunk && vertex) || t->n == 0), "NULL argument");
         check_table(t);
         use_device(c);
@@ -710,7 +691,7 @@ int st_dev_pack_compressed(st_ctx *c, const st_table *t, const uint32_t *order, 
 
 int st_dev_kmeans(st_ctx *c, const float *const *cols, int32_t d, uint64_t n, int32_t k, int32_t iters,
                   const double *draws, uint64_t ndraws, uint64_t *used, float *centroids, uint32_t *labels) {
-    return guarded([&] {
+    return guard([&] {
         ST_ARG(c && cols && d > 0 && k > 0 && iters >= 0 && centroids && labels, "bad argument");
         ST_ARG(draws || ndraws == 0, "draws is NULL");
         use_device(c);
@@ -723,7 +704,7 @@ int st_dev_kmeans(st_ctx *c, const float *const *cols, int32_t d, uint64_t n, in
 
 int st_dev_cluster1d(st_ctx *c, const float *const *cols, int32_t ncols, uint64_t n, int32_t iters,
                      const double *draws, uint64_t ndraws, uint64_t *used, float *centroids, uint8_t *labels) {
-    return guarded([&] {
+    return guard([&] {
         ST_ARG(c && cols && ncols > 0 && centroids && labels, "bad argument");
         use_device(c);
         begin_timing(c);
@@ -735,7 +716,7 @@ int st_dev_cluster1d(st_ctx *c, const float *const *cols, int32_t ncols, uint64_
 
 int st_dev_sog(st_ctx *c, const st_table *t, int32_t iters, const double *draws, uint64_t ndraws, uint64_t *used,
                st_sog_meta *meta, const st_sog_textures *out) {
-    return guarded([&] {
+    return guard([&] {
         ST_ARG(c && meta && out, "NULL argument");
         check_table(t);
         use_device(c);
@@ -749,7 +730,7 @@ int st_dev_sog(st_ctx *c, const st_table *t, int32_t iters, const double *draws,
 int st_dev_sog_file(st_ctx *c, const st_table *t, int32_t iters, const double *draws, uint64_t ndraws, uint64_t *used,
                     st_sog_meta *meta, const st_sog_textures *out, int32_t fd, uint16_t dos_time, uint16_t dos_date,
                     uint64_t *size) {
-    return guarded([&] {
+    return guard([&] {
         ST_ARG(c && meta && out && size && fd >= 0, "bad argument");
         check_table(t);
         use_device(c);
@@ -762,7 +743,7 @@ int st_dev_sog_file(st_ctx *c, const st_table *t, int32_t iters, const double *d
 
 // ---- multi-GPU building blocks ------------------------------------------------------
 int st_dev_minmax(st_ctx *c, const float *const *cols, int32_t ncols, uint64_t n, double *lo, double *hi) {
-    return guarded([&] {
+    return guard([&] {
         ST_ARG(c && cols && ncols > 0 && lo && hi, "bad argument");
         use_device(c);
         minmax_dev(c, cols, ncols, n, lo, hi);
@@ -770,7 +751,7 @@ int st_dev_minmax(st_ctx *c, const float *const *cols, int32_t ncols, uint64_t n
 }
 
 int st_dev_kmeans_prepare(st_ctx *c, const float *const *cols, int32_t d, uint64_t n) {
-    return guarded([&] {
+    return guard([&] {
         ST_ARG(c && cols && d > 0 && n > 0, "bad argument");
         use_device(c);
         dist_prepare(c, cols, d, n);
@@ -779,7 +760,7 @@ int st_dev_kmeans_prepare(st_ctx *c, const float *const *cols, int32_t d, uint64
 
 int st_dev_kmeans_assign(st_ctx *c, const float *const *cols, int32_t d, uint64_t n, int32_t k,
                          const float *centroids, uint32_t *labels) {
-    return guarded([&] {
+    return guard([&] {
         ST_ARG(c && cols && d > 0 && n > 0 && k > 0 && centroids && labels, "bad argument");
         use_device(c);
         dist_assign(c, cols, d, n, k, centroids, labels);
@@ -788,7 +769,7 @@ int st_dev_kmeans_assign(st_ctx *c, const float *const *cols, int32_t d, uint64_
 
 int st_dev_kmeans_init_rows(st_ctx *c, const double *draws, uint64_t ndraws, uint64_t n, int32_t k, uint32_t *rows,
                             uint64_t *used) {
-    return guarded([&] {
+    return guard([&] {
         ST_ARG(c && (draws || ndraws == 0) && k > 0 && rows && used, "bad argument");
         use_device(c);
         kmeans_init_rows(c, draws, ndraws, n, k, rows, used);
@@ -797,7 +778,7 @@ int st_dev_kmeans_init_rows(st_ctx *c, const double *draws, uint64_t ndraws, uin
 
 int st_dev_gather_rows(st_ctx *c, const float *const *cols, int32_t d, uint64_t n_local, uint64_t offset,
                        const uint32_t *rows, int32_t k, float *out) {
-    return guarded([&] {
+    return guard([&] {
         ST_ARG(c && cols && d > 0 && k > 0 && rows && out, "bad argument");
         use_device(c);
         gather_owned_rows(c, cols, d, n_local, offset, rows, k, out);
@@ -806,7 +787,7 @@ int st_dev_gather_rows(st_ctx *c, const float *const *cols, int32_t d, uint64_t 
 
 int st_dev_kmeans_partials(st_ctx *c, const float *const *cols, int32_t d, uint64_t n, int32_t nseg, int32_t k,
                            const uint32_t *labels, double *sums, double *sabs, int32_t *emin, uint32_t *counts) {
-    return guarded([&] {
+    return guard([&] {
         ST_ARG(c && cols && d > 0 && n > 0 && k > 0 && labels && sums && sabs && emin && counts, "bad argument");
         use_device(c);
         dist_partials(c, cols, d, n, nseg, k, labels, sums, sabs, emin, counts);
@@ -815,7 +796,7 @@ int st_dev_kmeans_partials(st_ctx *c, const float *const *cols, int32_t d, uint6
 
 int st_dev_kmeans_seqsum(st_ctx *c, int32_t d, int32_t k, int32_t seg, const uint32_t *pairs, uint32_t npairs,
                          double *running, const int32_t *emin, const double *sabs) {
-    return guarded([&] {
+    return guard([&] {
         ST_ARG(c && (npairs == 0 || (pairs && running && emin && sabs)), "bad argument");
         use_device(c);
         dist_seqsum(c, d, k, seg, pairs, npairs, running, emin, sabs);
@@ -825,7 +806,7 @@ int st_dev_kmeans_seqsum(st_ctx *c, int32_t d, int32_t k, int32_t seg, const uin
 int st_dev_kmeans_finish(st_ctx *c, int32_t d, int32_t k, const double *sums, const double *sabs,
                          const int32_t *emin, const uint32_t *counts, float *centroids, uint32_t *pending,
                          uint32_t *npending) {
-    return guarded([&] {
+    return guard([&] {
         ST_ARG(c && d > 0 && k > 0 && sums && sabs && emin && counts && centroids && pending && npending,
                "bad argument");
         use_device(c);
@@ -835,7 +816,7 @@ int st_dev_kmeans_finish(st_ctx *c, int32_t d, int32_t k, const double *sums, co
 
 int st_dev_kmeans_average(st_ctx *c, int32_t d, int32_t k, const uint32_t *pairs, uint32_t npairs,
                           const double *running, const uint32_t *counts, float *centroids) {
-    return guarded([&] {
+    return guard([&] {
         ST_ARG(c && d > 0 && k > 0 && (npairs == 0 || (pairs && running)) && counts && centroids, "bad argument");
         use_device(c);
         dist_average(c, d, k, pairs, npairs, running, counts, centroids);
@@ -844,7 +825,7 @@ int st_dev_kmeans_average(st_ctx *c, int32_t d, int32_t k, const uint32_t *pairs
 
 int st_dev_cluster1d_codebook(st_ctx *c, const float *centroids, const uint32_t *labels, uint64_t total,
                               float *codebook256, uint8_t *labels8) {
-    return guarded([&] {
+    return guard([&] {
         ST_ARG(c && centroids && codebook256 && (total == 0 || (labels && labels8)), "bad argument");
         use_device(c);
         codebook_dev(c, centroids, labels, total, codebook256, labels8);
@@ -854,7 +835,7 @@ int st_dev_cluster1d_codebook(st_ctx *c, const float *centroids, const uint32_t 
 int st_dev_sog_scatter(st_ctx *c, const st_table *local, const uint32_t *pos, const double lo[3], const double hi[3],
                        const uint8_t *scale_labels, const uint8_t *color_labels, const uint32_t *shn_labels,
                        st_sog_meta *meta, const st_sog_textures *out) {
-    return guarded([&] {
+    return guard([&] {
         ST_ARG(c && (pos || local->n == 0) && lo && hi && meta && out, "bad argument");
         check_table(local);
         use_device(c);
@@ -864,7 +845,7 @@ int st_dev_sog_scatter(st_ctx *c, const st_table *local, const uint32_t *pos, co
 
 int st_dev_sog_shn_centroids(st_ctx *c, const uint8_t *codebook_labels, int32_t sh_coeffs, int32_t palette,
                              uint8_t *out) {
-    return guarded([&] {
+    return guard([&] {
         ST_ARG(c && codebook_labels && sh_coeffs > 0 && palette > 0 && out, "bad argument");
         use_device(c);
         shn_centroids_dev(c, codebook_labels, sh_coeffs, palette, out);

@@ -45,6 +45,48 @@ void sog_file_check(int fd);
 void write_at(int fd, const uint8_t *p, uint64_t n, uint64_t off);
 void sog_file_truncate(int fd, uint64_t size);
 
+// ---- host steps the one-call writeSog forms share (st_host_api.hip) ----------
+// the columns writeSog reads (write-sog.ts:110-370): the other columns of a PLY (normals, extra
+// properties) are not uploaded
+const std::vector<std::string> &sog_columns();
+// device textures of writeSog for n rows of band C in c's workspace (slots h.s.*)
+st_sog_textures sog_textures(st_ctx *c, uint64_t n, int C);
+// where a one-call form leaves writeSog's result: the textures and meta on the host, the .sog
+// archive in a malloc'd buffer (st_free), or the archive in an open file
+struct SogSink {
+    enum Kind { TO_HOST, TO_BUFFER, TO_FILE } kind;
+    st_sog_meta *meta = nullptr;  // TO_HOST
+    const st_sog_textures *tex = nullptr;
+    uint8_t **out = nullptr;   // TO_BUFFER
+    uint64_t *size = nullptr;  // TO_BUFFER, TO_FILE: the archive's bytes
+    int fd = -1;               // TO_FILE
+    uint16_t dos_time = 0, dos_date = 0;
+    static SogSink textures(st_sog_meta *m, const st_sog_textures *t) {
+        SogSink s{TO_HOST};
+        s.meta = m, s.tex = t;
+        return s;
+    }
+    static SogSink buffer(uint8_t **out, uint64_t *size, uint16_t dos_time, uint16_t dos_date) {
+        SogSink s{TO_BUFFER};
+        s.out = out, s.size = size, s.dos_time = dos_time, s.dos_date = dos_date;
+        return s;
+    }
+    static SogSink file(int fd, uint64_t *size, uint16_t dos_time, uint16_t dos_date) {
+        SogSink s{TO_FILE};
+        s.fd = fd, s.size = size, s.dos_time = dos_time, s.dos_date = dos_date;
+        return s;
+    }
+    bool ok() const { return kind == TO_HOST ? meta && tex : kind == TO_BUFFER ? out && size : size && fd >= 0; }
+};
+// the device textures dt of `count` rows, described by meta, into the sink: every host texture
+// pointer checked (ST_ERR_ARG), the archive built by sog_bundle_dev
+void sog_deliver(st_ctx *c, const st_sog_textures &dt, const st_sog_meta &meta, uint64_t count, const SogSink &to);
+// writeSog of host tables on a group (st_multi.hip), table t after its processDataTable actions
+// when `actions`: the body of the st_group_sog* forms and of every one-call form's group branch
+void group_sog_to(st_group *g, const st_table *const *tabs, int ntab, const uint64_t *splits,
+                  const st_action *const *actions, const int32_t *nactions, int iters, const double *draws,
+                  uint64_t ndraws, uint64_t *used, const SogSink &to);
+
 // ---- host: the .sog container (st_zip.cpp) ----------------------------------
 // JSON text of a JS number (Number::toString as JSON.stringify emits it; non-finite -> null)
 std::string js_number(double v);

@@ -112,6 +112,95 @@ def test_st_num_gpus_rejects_a_bad_value():
     assert rc == sh.ST_ERR_ARG and 'ST_NUM_GPUS' in msg
 
 
+def _sog_form_calls(L):
+    """[(id, call)]: each of the nine one-call writeSog forms with a NULL context or group, a NULL
+    table and NULL outputs (st_sog_file also with fd = -1); call() returns the form's return code.
+    `handle` stands in for a context or group where another argument is the NULL one: the argument
+    checks come before anything reads it.  The three chain forms select their device before they
+    look at the table, so their NULL-table call passes a NULL context as well."""
+    import ctypes
+    n = 8
+    cols = {k: np.zeros(n, np.float32) for k in ('x', 'y', 'z', 'scale_0', 'scale_1', 'scale_2', 'f_dc_0', 'f_dc_1',
+                                                 'f_dc_2', 'opacity', 'rot_0', 'rot_1', 'rot_2', 'rot_3')}
+    t, tt = sh.make_table(cols), sh.make_ttable(cols)
+    tp, ttp = ctypes.byref(t), ctypes.byref(tt)
+    tabs = (ctypes.POINTER(sh.Table) * 1)(ctypes.pointer(t))
+    zeros = ctypes.create_string_buffer(1 << 16)
+    handle = ctypes.cast(zeros, ctypes.c_void_p)
+    draws = np.zeros(16)
+    it, dr, nd = ctypes.c_int32(1), sh._vp(draws), ctypes.c_uint64(len(draws))
+    used, size = ctypes.c_uint64(0), ctypes.c_uint64(0)
+    meta, tex = sh.SogMeta(), sh.SogTextures()
+    out = ctypes.c_void_p()
+    up, mp, xp, op, sp = (ctypes.byref(x) for x in (used, meta, tex, out, size))
+    hdr = sh.PlyHeader()
+    hp = ctypes.byref(hdr)
+    z16, i0, fd0, bad_fd = ctypes.c_uint16(0), ctypes.c_int32(0), ctypes.c_int32(0), ctypes.c_int32(-1)
+    acts = (ctypes.POINTER(sh.Action) * 1)()
+    nacts = (ctypes.c_int32 * 1)(0)
+    one = ctypes.c_int32(1)
+    keep = (t, tt, tabs, zeros, draws, used, size, meta, tex, out, hdr, acts, nacts)
+
+    def form(name, *args):
+        return lambda: (keep, getattr(L, name)(*args))[1]
+
+    calls = []
+    for what, c, tab, ttab, tb, h in (('ctx', None, tp, ttp, tabs, hp), ('table', handle, None, None, None, None)):
+        chain_c = c if what == 'ctx' else None
+        calls += [
+            (f'st_sog-{what}', form('st_sog', c, tab, it, dr, nd, up, mp, xp)),
+            (f'st_sog_bundle-{what}', form('st_sog_bundle', c, tab, it, dr, nd, up, z16, z16, op, sp)),
+            (f'st_sog_file-{what}', form('st_sog_file', c, tab, it, dr, nd, up, fd0, z16, z16, sp)),
+            (f'st_sog_process-{what}', form('st_sog_process', chain_c, ttab, None, i0, it, dr, nd, up, mp, xp)),
+            (f'st_sog_bundle_process-{what}',
+             form('st_sog_bundle_process', chain_c, ttab, None, i0, it, dr, nd, up, z16, z16, op, sp)),
+            (f'st_ply_sog_bundle-{what}',
+             form('st_ply_sog_bundle', chain_c, fd0, h, i0, None, i0, it, dr, nd, up, z16, z16, op, sp)),
+            (f'st_group_sog-{what}', form('st_group_sog', c, tb, one, None, it, dr, nd, up, mp, xp)),
+            (f'st_group_sog_bundle-{what}',
+             form('st_group_sog_bundle', c, tb, one, None, it, dr, nd, up, z16, z16, op, sp)),
+            (f'st_group_sog_bundle_process-{what}',
+             form('st_group_sog_bundle_process', c, tb, one, None, acts, nacts, it, dr, nd, up, z16, z16, op, sp)),
+        ]
+    calls += [
+        ('st_sog-outputs', form('st_sog', handle, tp, it, dr, nd, up, None, None)),
+        ('st_sog_bundle-outputs', form('st_sog_bundle', handle, tp, it, dr, nd, up, z16, z16, None, None)),
+        ('st_sog_file-outputs', form('st_sog_file', handle, tp, it, dr, nd, up, fd0, z16, z16, None)),
+        ('st_sog_file-fd', form('st_sog_file', handle, tp, it, dr, nd, up, bad_fd, z16, z16, sp)),
+        ('st_sog_process-outputs', form('st_sog_process', handle, ttp, None, i0, it, dr, nd, up, None, None)),
+        ('st_sog_bundle_process-outputs',
+         form('st_sog_bundle_process', handle, ttp, None, i0, it, dr, nd, up, z16, z16, None, None)),
+        ('st_ply_sog_bundle-outputs',
+         form('st_ply_sog_bundle', handle, fd0, hp, i0, None, i0, it, dr, nd, up, z16, z16, None, None)),
+        ('st_group_sog-outputs', form('st_group_sog', handle, tabs, one, None, it, dr, nd, up, None, None)),
+        ('st_group_sog_bundle-outputs',
+         form('st_group_sog_bundle', handle, tabs, one, None, it, dr, nd, up, z16, z16, None, None)),
+        ('st_group_sog_bundle_process-outputs',
+         form('st_group_sog_bundle_process', handle, tabs, one, None, acts, nacts, it, dr, nd, up, z16, z16, None,
+              None)),
+    ]
+    return calls
+
+
+def test_sog_forms_refuse_null_arguments(L, monkeypatch):
+    """the nine one-call writeSog forms (st_sog, st_sog_bundle, st_sog_file, st_sog_process,
+    st_sog_bundle_process, st_ply_sog_bundle and the three st_group_* forms) return ST_ERR_ARG with
+    these st_last_error() texts for a NULL context or group, a NULL table, NULL outputs and, for
+    st_sog_file, a negative descriptor -- before any device call, so without a GPU"""
+    monkeypatch.delenv('ST_NUM_GPUS', raising=False)
+    monkeypatch.delenv('ST_DEFAULT_GROUP_RANKS', raising=False)
+    want = {'st_sog_file-ctx': 'bad argument', 'st_sog_file-table': 'bad argument',
+            'st_sog_file-outputs': 'bad argument', 'st_sog_file-fd': 'bad argument'}
+    calls = _sog_form_calls(L)
+    assert len(calls) == 28 and len({k for k, _ in calls}) == 28
+    for key, call in calls:
+        rc = call()
+        msg = L.st_last_error().decode()
+        print(key, rc, repr(msg))
+        assert rc == sh.ST_ERR_ARG, (key, rc, msg)
+        assert msg == want.get(key, 'NULL argument'), (key, msg)
+
+
 def _rccl_python(env_value=None, torch_first=True):
     """st_rccl_info in a fresh Python process (torch imported first, as the bench does)"""
     import json
