@@ -190,6 +190,11 @@ double st_o_log(double x)
     return dk * ln2_hi - ((s * (f - R) - dk * ln2_lo) - f);
 }
 
+void st_o_log_n(uint64_t n, const double *x, double *out)
+{
+    for (uint64_t i = 0; i < n; ++i) out[i] = st_o_log(x[i]);
+}
+
 static inline double sigmoid(double v) { return 1 / (1 + st_o_exp(-v)); } /* utils/math.ts:1 */
 
 /* ------------------------------------------------------------------------- */

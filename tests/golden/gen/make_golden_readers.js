@@ -67,7 +67,10 @@ class Gen {
 }
 
 class Fixture {
-    constructor(name) { this.name = name; this.arrays = {}; this.chunks = []; this.offset = 0; this.meta = {}; }
+    constructor(name, generator) {
+        this.name = name; this.arrays = {}; this.chunks = []; this.offset = 0; this.meta = {};
+        this.generator = generator || 'tests/golden/gen/make_golden_readers.js';
+    }
     add(key, arr, shape) {
         const dtype = { Float32Array: 'f4', Uint8Array: 'u1' }[arr.constructor.name];
         if (!dtype) throw new Error(`bad array type for ${key}`);
@@ -81,7 +84,7 @@ class Fixture {
     save() {
         fs.writeFileSync(path.join(OUT, `${this.name}.bin`), Buffer.concat(this.chunks));
         fs.writeFileSync(path.join(OUT, `${this.name}.json`), JSON.stringify({
-            generator: 'tests/golden/gen/make_golden_readers.js (reference modules type-erased by build_ref_readers.py)',
+            generator: `${this.generator} (reference modules type-erased by build_ref_readers.py)`,
             reference: '@playcanvas/splat-transform 0.10.1 @ /root/reference',
             meta: this.meta,
             arrays: this.arrays
@@ -258,8 +261,9 @@ const run = async (format, bytes) => {
     try { return await READERS[format](fh); } finally { await fh.close(); }
 };
 
-const main = async () => {
-    const fx = new Fixture('readers');
+// the two recorders of a fixture set: ok() runs a file the reader accepts and records its bytes and
+// columns, bad() one it rejects and records the message
+const recorders = (fx) => {
     fx.meta.cases = [];
     fx.meta.errors = [];
 
@@ -284,6 +288,12 @@ const main = async () => {
         if (bytes.length) fx.add(`${name}_file`, new Uint8Array(bytes));
         fx.meta.errors.push({ name, format, size: bytes.length, message, note: note || '' });
     };
+    return { ok, bad };
+};
+
+const main = async () => {
+    const fx = new Fixture('readers');
+    const { ok, bad } = recorders(fx);
 
     // ---- .splat
     for (const n of [1, 255, 257, 1025]) {
@@ -360,4 +370,7 @@ const main = async () => {
     fs.rmdirSync(dir, { recursive: true });
 };
 
-main().catch((e) => { console.error(e); process.exit(1); });
+// (make_golden_readers_edges.js builds its files with the same functions)
+module.exports = { Gen, Fixture, recorders, makeKsplat, makeSpzRaw, gz, dir };
+
+if (require.main === module) main().catch((e) => { console.error(e); process.exit(1); });
