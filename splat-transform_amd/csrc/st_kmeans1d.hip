@@ -13,6 +13,18 @@
 // parallel when every value is a multiple of 2^e and sum|x| < 2^(e+53) (then
 // every partial sum is exact, so any order equals calcAverage's sequential
 // sum), otherwise in the reference's order.
+//
+// The iterations (kmeans1d_loop chooses one per call):
+//   accumulating, queued        k <= 256 (cluster1d's codebooks): the assign accumulates the
+//                               clusters' partials, no member sort; up to 8 uncertified clusters
+//                               are updated by the k_ff_batch family with no read-back
+//   accumulating, synchronised  the rerun of such a call after more than 8 clusters failed the
+//                               certificate in one iteration (ERR_K1_MANY): the flagged count is
+//                               read back, the flagged clusters' members are gathered (wave
+//                               chain up to 8 clusters, tile kernels past that) and replayed
+//   general                     k > 256: assign, (label, value) pairs, radix sort by label,
+//                               chunked sums, chunked replay, sequential chain, re-seeding
+// The multi-GPU update (st_dist.hip) uses the pieces at the end of the file.
 #include "st_jsmath.h"
 #include "st_kmeans.h"
 #include "st_replay.h"
@@ -98,22 +110,12 @@ __device__ inline uint32_t kd1_walk(double p, int k, V val, I idx) {
     return mini;
 }
 
-template <bool LDS>
+// the walk with the centroids in global memory: k > KD1_LDS
 __global__ __launch_bounds__(256) void k_kd1_assign(const float *__restrict__ pts, uint64_t n,
                                                     const float *__restrict__ cen, const uint32_t *__restrict__ order,
                                                     int k, uint32_t *__restrict__ labels) {
-    __shared__ float sv[LDS ? KD1_LDS : 1];
-    __shared__ uint32_t si[LDS ? KD1_LDS : 1];
-    if (LDS) {
-        for (int i = threadIdx.x; i < k; i += blockDim.x) {
-            const uint32_t o = order[i];
-            si[i] = o;
-            sv[i] = cen[o];
-        }
-        __syncthreads();
-    }
-    auto val = [&](uint32_t pos) -> float { return LDS ? sv[pos] : cen[order[pos]]; };
-    auto idx = [&](uint32_t pos) -> uint32_t { return LDS ? si[pos] : order[pos]; };
+    auto val = [&](uint32_t pos) -> float { return cen[order[pos]]; };
+    auto idx = [&](uint32_t pos) -> uint32_t { return order[pos]; };
     const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
     for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride)
         labels[i] = kd1_walk((double)pts[i], k, val, idx);
@@ -195,96 +197,20 @@ __global__ __launch_bounds__(256) void k_kd1_assign_fast(const float *__restrict
     }
 }
 
-// ---- fused iteration for k <= 256 (cluster1d's codebooks) ------------------------------
+// ---- counting sort by label for k <= 256 (the sharded member order, seg_label_sort1d) ----
 // The member sort only has to lay each cluster's values out in ascending point order: the
 // label is an 8-bit digit, so one counting-sort pass does it, and the cluster starts are
-// the scanned digit counts.  Assign + tile histogram in one kernel (byte labels out), the
-// scan of the (digit, tile) counts, then a scatter that moves 4-byte values only: 14 bytes
-// per point against 36 for assign -> (label, value) pairs -> radix pass -> bounds.
+// the scanned digit counts.  A tile histogram of the labels, the scan of the (digit, tile)
+// counts, then a scatter that moves 4-byte values only.
 constexpr int F1_T = 256, F1_ROWS = 16, F1_TILE = F1_T * F1_ROWS, F1_WAVES = F1_T / 64;
 
-// k_kd1_assign_fast's bracket assign over one 4,096-point tile per workgroup; lab8 = labels
-// as bytes, labels (if non-null) the u32 result, hist[d * ntiles + tile] = count of digit d
-__global__ __launch_bounds__(F1_T) void k_kd1_assign_hist(const float *__restrict__ pts, uint64_t n,
-                                                         const float *__restrict__ cen,
-                                                         const uint32_t *__restrict__ order, int k,
-                                                         uint32_t *__restrict__ labels, uint8_t *__restrict__ lab8,
-                                                         uint32_t *__restrict__ hist, uint32_t ntiles) {
-    __shared__ float sv[256];
-    __shared__ uint32_t si[256];
-    __shared__ uint16_t cc[256];
-    __shared__ uint32_t first[KD1_CELLS + 1];
-    __shared__ uint32_t h[256];
-    h[threadIdx.x] = 0;
-    for (int i = threadIdx.x; i < k; i += blockDim.x) {
-        const uint32_t o = order[i];
-        si[i] = o;
-        sv[i] = cen[o];
-    }
-    const uint64_t base = (uint64_t)blockIdx.x * F1_TILE;
-    float pv[F1_ROWS];  // the tile's points in flight while the tables are built
-#pragma unroll
-    for (int r = 0; r < F1_ROWS; ++r) {
-        const uint64_t i = base + (uint64_t)r * F1_T + threadIdx.x;
-        pv[r] = i < n ? pts[i] : 0.f;
-    }
-    __syncthreads();
-    const float lo = sv[0], hi = sv[k - 1];
-    const float span = hi - lo;
-    const float inv = (span > 0.f && span < __builtin_inff()) ? (float)KD1_CELLS / span : 0.f;
-    auto cell = [&](float x) -> int {
-        const float t = (x - lo) * inv;
-        return (int)__builtin_fminf(__builtin_fmaxf(t, 0.f), (float)(KD1_CELLS - 1));
-    };
-    for (int i = threadIdx.x; i < k; i += blockDim.x) cc[i] = (uint16_t)cell(sv[i]);
-    __syncthreads();
-    for (int g = threadIdx.x; g <= KD1_CELLS; g += blockDim.x) {
-        int a = 0, b = k;
-        while (a < b) {
-            const int m = (a + b) >> 1;
-            if ((int)cc[m] < g) a = m + 1;
-            else b = m;
-        }
-        first[g] = (uint32_t)a;
-    }
-    __syncthreads();
-    auto dist = [&](int pos, double p) {
-        const double v = (double)sv[pos] - p;
-        return 0.0 + v * v;
-    };
-    auto val = [&](uint32_t pos) -> float { return sv[pos]; };
-    auto idx = [&](uint32_t pos) -> uint32_t { return si[pos]; };
-#pragma unroll
-    for (int r = 0; r < F1_ROWS; ++r) {
-        const uint64_t i = base + (uint64_t)r * F1_T + threadIdx.x;
-        if (i >= n) break;
-        const float pf = pv[r];
-        const double p = pf;
-        const int g = cell(pf);
-        int u = (int)first[g];
-        const int ue = (int)first[g + 1];
-        while (u < ue && sv[u] <= pf) ++u;
-        const int L = u - 1, R = u;
-        const double dl = L >= 0 ? dist(L, p) : __builtin_inf();
-        const double dr = R < k ? dist(R, p) : __builtin_inf();
-        const double m = __builtin_fmin(dl, dr);
-        const bool tie = dl == dr || (L >= 1 && dist(L - 1, p) == m) || (R + 1 < k && dist(R + 1, p) == m);
-        const uint32_t lab = !tie ? si[dl < dr ? L : R] : kd1_walk(p, k, val, idx);
-        lab8[i] = (uint8_t)lab;
-        if (labels) labels[i] = lab;
-        atomicAdd(&h[lab], 1u);
-    }
-    __syncthreads();
-    hist[(uint64_t)threadIdx.x * ntiles + blockIdx.x] = h[threadIdx.x];
-}
-
-// stable counting-sort pass on the byte labels moving the value bits only: each wave ranks its
-// 1,024 points with ballots over the `bits` label bits, the tile is reordered by label in LDS
-// and each label's run is stored contiguously at its scanned offset
-template <typename L>
-__global__ __launch_bounds__(F1_T) void k_lab_scatter(const L *__restrict__ lab8, const float *__restrict__ pts,
-                                                      uint64_t n, int bits, const uint32_t *__restrict__ offs,
-                                                      uint32_t ntiles, uint32_t *__restrict__ ovals) {
+// stable counting-sort pass on the labels (< 256) moving the value bits only: each wave ranks
+// its 1,024 points with ballots over the `bits` label bits, the tile is reordered by label in
+// LDS and each label's run is stored contiguously at its scanned offset
+__global__ __launch_bounds__(F1_T) void k_lab_scatter(const uint32_t *__restrict__ labels,
+                                                      const float *__restrict__ pts, uint64_t n, int bits,
+                                                      const uint32_t *__restrict__ offs, uint32_t ntiles,
+                                                      uint32_t *__restrict__ ovals) {
     __shared__ uint32_t wcount[F1_WAVES][256];
     __shared__ uint32_t wbase[F1_WAVES][256];
     __shared__ uint32_t goff[256];
@@ -304,7 +230,7 @@ __global__ __launch_bounds__(F1_T) void k_lab_scatter(const L *__restrict__ lab8
     for (int r = 0; r < F1_ROWS; ++r) {
         const uint64_t e = wb + (uint64_t)r * 64 + lane;
         const bool valid = e < n;
-        dg[r] = valid ? (uint32_t)lab8[e] : 0u;
+        dg[r] = valid ? labels[e] : 0u;
         v[r] = valid ? __builtin_bit_cast(uint32_t, pts[e]) : 0u;
     }
 #pragma unroll
@@ -955,7 +881,7 @@ uint32_t a1_grid(uint32_t ntiles) {
     return (ntiles + per - 1) / per;
 }
 
-// k_kd1_assign_hist's bracket assign with the centroid order built in the workgroup (the
+// k_kd1_assign_fast's bracket assign with the centroid order built in the workgroup (the
 // stable sort of KdTree's build is a rank by (sort key, index)), over the tiles
 // blockIdx.x, blockIdx.x + gridDim.x, ...; part[blockIdx.x * 256 + c] = cluster c's partial
 template <bool BOUNDS>
@@ -1920,13 +1846,175 @@ bool assign1d(st_ctx *c, const float *pts, uint64_t n, int k, const float *cen, 
         ST_LAUNCH_CHECK();
         return keys != nullptr;
     }
-    hipLaunchKernelGGL(k_kd1_assign<false>, dim3(g), dim3(256), 0, c->stream, pts, n, cen, corder, k, labels);
+    hipLaunchKernelGGL(k_kd1_assign, dim3(g), dim3(256), 0, c->stream, pts, n, cen, corder, k, labels);
     ST_LAUNCH_CHECK();
     return false;
 }
 
-void kmeans1d_loop(st_ctx *c, const float *pts, const float *const *dcols, uint64_t n, int k, int iters,
-                   const double *ddraws, uint64_t ndraws, State *dstate, float *cen, uint32_t *labels) {
+namespace {
+
+// bits of a label below k (at least 1): the digits of the member sorts
+int label_bits(int k) {
+    int bits = 1;
+    while ((1ull << bits) < (uint64_t)k) ++bits;
+    return bits;
+}
+
+// ST_DEBUG: the clusters whose seq_flag equals v (a read-back; waits for the stream)
+uint32_t count_flag(st_ctx *c, const uint32_t *seq_flag, int k, uint32_t v) {
+    std::vector<uint32_t> f(k);
+    ST_HIP(hipMemcpyAsync(f.data(), seq_flag, sizeof(uint32_t) * k, hipMemcpyDeviceToHost, c->stream));
+    ST_HIP(hipStreamSynchronize(c->stream));
+    uint32_t m = 0;
+    for (uint32_t x : f) m += x == v;
+    return m;
+}
+
+// The accumulating iteration (0 < n < 2^32, k <= 256): k_kd1_assign_acc labels the points and
+// accumulates every cluster's partials, k_kd1_final certifies the sums, scans the starts and
+// re-seeds.  Queued (the default), the k_ff_batch family then updates up to ff_max flagged
+// clusters with no read-back; more set ERR_K1_MANY and kmeans_dev reruns the call synchronised
+// (c->k1_sync).  Synchronised, the flagged count is read back each iteration and the flagged
+// clusters' members are gathered (the wave chain k_ff_count / scan / scatter up to ff_max of
+// them, the tile kernels k_flag_* past that) for the chunked replay and the sequential chain.
+void k1_accumulating(st_ctx *c, const float *pts, const float *const *dcols, uint64_t n, int k, int iters,
+                     const double *ddraws, uint64_t ndraws, State *dstate, float *cen, uint32_t *labels) {
+    auto *vals = wsT<uint32_t>(c, "k1.vals", n);
+    auto *start = wsT<uint32_t>(c, "k1.start", (size_t)k + 1);
+    auto *seq_flag = wsT<uint32_t>(c, "k1.seqflag", (size_t)k);
+    auto *emin_c = wsT<int32_t>(c, "k1.emin", (size_t)k);
+    auto *sabs_c = wsT<double>(c, "k1.sabs", (size_t)k);
+    auto *cand_buf = wsT<__int128>(c, "k1.cands", (size_t)k * CAND_MAX);
+    const uint64_t chcap = n / FL_CH + (uint64_t)k + 1;  // the flagged replay's shorter chunks
+    auto *ch_cnt = wsT<uint32_t>(c, "k1.chcnt", (size_t)k);
+    auto *ch_first = wsT<uint32_t>(c, "k1.chfirst", (size_t)k + 1);
+    auto *chunks = wsT<Chunk>(c, "k1.chunks", chcap);
+    auto *rp_csum = wsT<__int128>(c, "k1.rpcsum", chcap);
+    auto *rp_ccnt = wsT<uint32_t>(c, "k1.rpccnt", chcap);
+    auto *rp_cof = wsT<uint32_t>(c, "k1.rpcof", chcap);
+    auto *rp_ctot = wsT<uint32_t>(c, "k1.rpctot", (size_t)k);
+    auto *rp_total = wsT<__int128>(c, "k1.rptotal", (size_t)k);
+    const int kbits = label_bits(k);
+    const uint32_t ntiles = (uint32_t)((n + F1_TILE - 1) / F1_TILE);
+    auto *lab8 = wsT<uint8_t>(c, "k1.lab8", n);
+    auto *fhist = wsT<uint32_t>(c, "k1.fhist", (size_t)256 * ntiles);
+    const uint32_t G = a1_grid(ntiles);
+    auto *part = wsT<Part1>(c, "k1.part", (size_t)G * 256);
+    auto *cnt_c = wsT<uint32_t>(c, "k1.cnt", (size_t)k);
+    auto *fstart = wsT<uint32_t>(c, "k1.fstart", (size_t)k + 1);
+    auto *ticket = wsT<uint32_t>(c, "k1.ticket", 1);
+    auto *dinfo = wsT<uint32_t>(c, "k1.info", 2);
+    auto *bnd = wsT<Bnd1>(c, "k1.bnd", 256);
+    // the points' min / max keys (kmeans_dev's 1-D init)
+    const uint32_t *mm = wsT<uint32_t>(c, "km.mm", 2);
+    auto *hinfo = static_cast<uint32_t *>(pinned_slot(c, "k1.info", 8));
+    ST_HIP(hipMemsetAsync(ticket, 0, sizeof(uint32_t), c->stream));
+    // the three-pass flagged update (k_ff_batch / k_ff_bscan / k_ff_place + k_ff_finish)
+    const uint32_t nbt = (uint32_t)((n + FB_PTS - 1) / FB_PTS);
+    auto *ffz = wsT<uint32_t>(c, "k1.ffz", FF_MAX);
+    auto *ffcnt = wsT<uint32_t>(c, "k1.ffcnt", (size_t)FF_MAX * nbt);
+    auto *ffpos = wsT<uint32_t>(c, "k1.ffpos", (size_t)FF_MAX * nbt);
+    auto *fflist = wsT<uint32_t>(c, "k1.fflist", FF_MAX + 1);
+    auto *ffpool = wsT<__int128>(c, "k1.ffpool", (size_t)FF_MAX * CAND_MAX);
+    auto *ffagg = wsT<FAgg>(c, "k1.ffagg", (size_t)FF_MAX * nbt);
+    auto *fftot = wsT<FAgg>(c, "k1.fftot", FF_MAX);
+    auto *ffscr = wsT<float>(c, "k1.ffscr", (size_t)nbt * FB_PTS);
+    // queued: no read-back per iteration (more than FF_MAX flagged clusters -> ERR_K1_MANY,
+    // and kmeans_dev reruns with k1_sync); otherwise the count decides the flagged path
+    const bool queued = !c->k1_sync && !getenv("ST_K1_TILES") && !getenv("ST_K1_SYNC");
+    // flagged clusters the wave kernels take (ST_K1_FF_MAX lowers it: tests of the rerun)
+    const uint32_t ff_max = getenv("ST_K1_FF_MAX") ? std::min<uint32_t>((uint32_t)atoi(getenv("ST_K1_FF_MAX")),
+                                                                        (uint32_t)FF_MAX)
+                                                   : (uint32_t)FF_MAX;
+    for (int it = 0; it < iters; ++it) {
+        {
+            KTimer kt(c, "k1.assign");
+            hipLaunchKernelGGL(k_kd1_assign_acc<true>, dim3(G), dim3(F1_T), 0, c->stream, pts, n, cen, k,
+                               it == iters - 1 ? labels : (uint32_t *)nullptr, lab8, ntiles, part, mm, bnd);
+            ST_LAUNCH_CHECK();
+        }
+        mark(c, "k1.assign");
+        KTimer kt(c, "k1.sum");
+        hipLaunchKernelGGL(k_kd1_final, dim3(k), dim3(256), 0, c->stream, part, G, k, n, cen, seq_flag, emin_c,
+                           sabs_c, cnt_c, start, fstart, ticket, dinfo, dcols, ddraws, ndraws, dstate,
+                           queued ? ff_max : 0xffffffffu, bnd, ffz);
+        ST_LAUNCH_CHECK();
+        if (queued) {
+            // the flagged path queued behind the final with no read-back: its kernels find
+            // the flagged clusters on the device and return at once when there are none
+            const unsigned gb = (unsigned)std::min<uint64_t>((nbt + 3) / 4, 2048);
+            hipLaunchKernelGGL(k_ff_batch, dim3(gb), dim3(256), 0, c->stream, lab8, pts, n, nbt, k, seq_flag,
+                               emin_c, sabs_c, ffscr, ffagg, fflist);
+            hipLaunchKernelGGL(k_ff_bscan, dim3(FF_MAX), dim3(FN_T), 0, c->stream, nbt, fflist, ffagg, fftot);
+            const unsigned gp = (unsigned)std::min<uint64_t>(((uint64_t)FF_MAX * nbt + 3) / 4, 4096);
+            hipLaunchKernelGGL(k_ff_place, dim3(gp), dim3(256), 0, c->stream, nbt, fflist, fstart, emin_c,
+                               sabs_c, ffscr, ffagg, ffz, vals, ffpool, ffcnt, ffpos, fftot);
+            hipLaunchKernelGGL(k_ff_finish, dim3(FF_MAX), dim3(FN_T), 0, c->stream, nbt, fflist, seq_flag,
+                               fstart, emin_c, sabs_c, fftot, vals, ffpool, ffcnt, ffpos, cand_buf,
+                               replay_cap(), cen, dstate);
+            ST_LAUNCH_CHECK();
+            if (getenv("ST_DEBUG")) {  // flagged clusters, their members and replay candidates
+                uint32_t hfl[FF_MAX + 1], hz[FF_MAX];
+                std::vector<uint32_t> f2(k), fs(k + 1);
+                ST_HIP(hipMemcpyAsync(hfl, fflist, sizeof hfl, hipMemcpyDeviceToHost, c->stream));
+                ST_HIP(hipMemcpyAsync(hz, ffz, sizeof hz, hipMemcpyDeviceToHost, c->stream));
+                ST_HIP(hipMemcpyAsync(f2.data(), seq_flag, 4 * k, hipMemcpyDeviceToHost, c->stream));
+                ST_HIP(hipMemcpyAsync(fs.data(), fstart, 4 * (k + 1), hipMemcpyDeviceToHost, c->stream));
+                ST_HIP(hipStreamSynchronize(c->stream));
+                fprintf(stderr, "[st k1] n=%llu flagged=%u", (unsigned long long)n, hfl[0]);
+                for (uint32_t f = 0; f < hfl[0] && f < (uint32_t)FF_MAX; ++f)
+                    fprintf(stderr, " c%u:members=%u,cands=%u,seq=%u", hfl[1 + f],
+                            fs[hfl[1 + f] + 1] - fs[hfl[1 + f]], hz[f], f2[hfl[1 + f]] == 2u ? 1u : 0u);
+                fprintf(stderr, "\n");
+            }
+            mark(c, "k1.update");
+            continue;
+        }
+        ST_HIP(hipMemcpyAsync(hinfo, dinfo, 8, hipMemcpyDeviceToHost, c->stream));
+        ST_HIP(hipStreamSynchronize(c->stream));
+        const uint32_t nflag = hinfo[0], ftotal = hinfo[1];
+        uint32_t nseq = 0;
+        if (nflag) {
+            // the flagged clusters' members in point order (fvals, starts fstart), then
+            // the chunked replay and, where it gives up, the sequential chain
+            if (nflag <= ff_max && !getenv("ST_K1_TILES")) {
+                const uint32_t nch = (uint32_t)((n + FF_CH - 1) / FF_CH);
+                hipLaunchKernelGGL(k_ff_count, dim3(G), dim3(256), 0, c->stream, lab8, n, nch, k, seq_flag, fhist);
+                hipLaunchKernelGGL(k_ff_scan, dim3(nflag), dim3(FS_T), 0, c->stream, fhist, nch, k, seq_flag,
+                                   fstart);
+                hipLaunchKernelGGL(k_ff_scatter, dim3(G), dim3(256), 0, c->stream, lab8, pts, n, nch, k, seq_flag,
+                                   fhist, vals);
+            } else {
+                hipLaunchKernelGGL(k_flag_tiles, dim3(G), dim3(F1_T), 0, c->stream, lab8, n, ntiles, k, seq_flag,
+                                   fhist);
+                hipLaunchKernelGGL(k_flag_scan, dim3(k), dim3(SC_T), 0, c->stream, fhist, ntiles, seq_flag, fstart);
+                hipLaunchKernelGGL(k_flag_scatter, dim3(G), dim3(F1_T), 0, c->stream, lab8, pts, n, ntiles, k,
+                                   kbits, seq_flag, fhist, vals);
+            }
+            ST_LAUNCH_CHECK();
+            // short chunks: the flagged clusters are few, their replay passes run over many
+            // workgroups at once
+            const uint64_t fch = ftotal / FL_CH + nflag + 1;
+            chunk_list(c, fstart, k, ch_cnt, ch_first, chunks, nullptr, FL_CH);
+            chunked_replay(c, vals, fstart, k, fch, chunks, ch_first, seq_flag, emin_c, sabs_c, rp_csum, rp_total,
+                           rp_ccnt, rp_cof, rp_ctot, cand_buf, cen, nullptr, nullptr);
+            if (getenv("ST_DEBUG")) nseq = count_flag(c, seq_flag, k, 2u);
+            hipLaunchKernelGGL(k_sum1d_seq, dim3(k), dim3(64), 0, c->stream, vals, fstart, seq_flag, cen);
+            ST_LAUNCH_CHECK();
+        }
+        if (getenv("ST_DEBUG"))
+            fprintf(stderr, "[st k1] n=%llu uncertified=%u sequential-fallback=%u\n", (unsigned long long)n, nflag,
+                    nseq);
+        mark(c, "k1.update");
+    }
+}
+
+// The general iteration (any k and n): the assign (its (label, value) pairs with it for
+// k <= KD1_LDS), a stable radix sort by label, every cluster's sums over SC_CH-member chunks,
+// the chunked replay and the sequential chain for the sums that fail the certificate, then
+// the empty clusters' re-seeding.
+void k1_general(st_ctx *c, const float *pts, const float *const *dcols, uint64_t n, int k, int iters,
+                const double *ddraws, uint64_t ndraws, State *dstate, float *cen, uint32_t *labels) {
     auto *keys = wsT<uint32_t>(c, "k1.keys", n);
     auto *vals = wsT<uint32_t>(c, "k1.vals", n);
     auto *start = wsT<uint32_t>(c, "k1.start", (size_t)k + 1);
@@ -1935,215 +2023,60 @@ void kmeans1d_loop(st_ctx *c, const float *pts, const float *const *dcols, uint6
     auto *sabs_c = wsT<double>(c, "k1.sabs", (size_t)k);
     auto *cand_buf = wsT<__int128>(c, "k1.cands", (size_t)k * CAND_MAX);
     const uint64_t maxch = n / SC_CH + (uint64_t)k + 1;
-    const uint64_t chcap = n / FL_CH + (uint64_t)k + 1;  // the flagged replay's shorter chunks
     auto *ch_cnt = wsT<uint32_t>(c, "k1.chcnt", (size_t)k);
     auto *ch_first = wsT<uint32_t>(c, "k1.chfirst", (size_t)k + 1);
-    auto *chunks = wsT<Chunk>(c, "k1.chunks", chcap);
+    auto *chunks = wsT<Chunk>(c, "k1.chunks", maxch);
     auto *acc = wsT<SumAcc>(c, "k1.acc", (size_t)k);
-    auto *rp_csum = wsT<__int128>(c, "k1.rpcsum", chcap);
-    auto *rp_ccnt = wsT<uint32_t>(c, "k1.rpccnt", chcap);
-    auto *rp_cof = wsT<uint32_t>(c, "k1.rpcof", chcap);
+    auto *rp_csum = wsT<__int128>(c, "k1.rpcsum", maxch);
+    auto *rp_ccnt = wsT<uint32_t>(c, "k1.rpccnt", maxch);
+    auto *rp_cof = wsT<uint32_t>(c, "k1.rpcof", maxch);
     auto *rp_ctot = wsT<uint32_t>(c, "k1.rpctot", (size_t)k);
     auto *rp_total = wsT<__int128>(c, "k1.rptotal", (size_t)k);
-    int kbits = 1;
-    while ((1ull << kbits) < (uint64_t)k) ++kbits;
-    // the fused iteration (k <= 256; ST_K1_PAIRS forces the general one, test hook): byte labels
-    // + tile counts, scan, value-only scatter
-    const bool fused = k <= 256 && n > 0 && n < (1ull << 32) && !getenv("ST_K1_PAIRS");
-    const uint32_t ntiles = (uint32_t)((n + F1_TILE - 1) / F1_TILE);
-    uint8_t *lab8 = fused ? wsT<uint8_t>(c, "k1.lab8", n) : nullptr;
-    // the sort-free iteration (k_kd1_assign_acc; ST_K1_SORT=1 keeps the member sort)
-    const bool accum = fused && !getenv("ST_K1_SORT");
-    uint32_t *fhist = fused ? wsT<uint32_t>(c, "k1.fhist", (size_t)256 * ntiles) : nullptr;
-    if (accum) {
-        const uint32_t G = a1_grid(ntiles);
-        auto *part = wsT<Part1>(c, "k1.part", (size_t)G * 256);
-        auto *cnt_c = wsT<uint32_t>(c, "k1.cnt", (size_t)k);
-        auto *fstart = wsT<uint32_t>(c, "k1.fstart", (size_t)k + 1);
-        auto *ticket = wsT<uint32_t>(c, "k1.ticket", 1);
-        auto *dinfo = wsT<uint32_t>(c, "k1.info", 2);
-        auto *bnd = wsT<Bnd1>(c, "k1.bnd", 256);
-        // the points' min / max keys (kmeans_dev's 1-D init)
-        const uint32_t *mm = wsT<uint32_t>(c, "km.mm", 2);
-        auto *hinfo = static_cast<uint32_t *>(pinned_slot(c, "k1.info", 8));
-        ST_HIP(hipMemsetAsync(ticket, 0, sizeof(uint32_t), c->stream));
-        // the three-pass flagged update (k_ff_batch / k_ff_bscan / k_ff_place + k_ff_finish)
-        const uint32_t nbt = (uint32_t)((n + FB_PTS - 1) / FB_PTS);
-        auto *ffz = wsT<uint32_t>(c, "k1.ffz", FF_MAX);
-        auto *ffcnt = wsT<uint32_t>(c, "k1.ffcnt", (size_t)FF_MAX * nbt);
-        auto *ffpos = wsT<uint32_t>(c, "k1.ffpos", (size_t)FF_MAX * nbt);
-        auto *fflist = wsT<uint32_t>(c, "k1.fflist", FF_MAX + 1);
-        auto *ffpool = wsT<__int128>(c, "k1.ffpool", (size_t)FF_MAX * CAND_MAX);
-        auto *ffagg = wsT<FAgg>(c, "k1.ffagg", (size_t)FF_MAX * nbt);
-        auto *fftot = wsT<FAgg>(c, "k1.fftot", FF_MAX);
-        auto *ffscr = wsT<float>(c, "k1.ffscr", (size_t)nbt * FB_PTS);
-        // queued: no read-back per iteration (more than FF_MAX flagged clusters -> ERR_K1_MANY,
-        // and kmeans_dev reruns with k1_sync); otherwise the count decides the flagged path
-        const bool queued = !c->k1_sync && !getenv("ST_K1_TILES") && !getenv("ST_K1_SYNC");
-        // flagged clusters the wave kernels take (ST_K1_FF_MAX lowers it: tests of the rerun)
-        const uint32_t ff_max = getenv("ST_K1_FF_MAX") ? std::min<uint32_t>((uint32_t)atoi(getenv("ST_K1_FF_MAX")),
-                                                                            (uint32_t)FF_MAX)
-                                                       : (uint32_t)FF_MAX;
-        for (int it = 0; it < iters; ++it) {
-            {
-                KTimer kt(c, "k1.assign");
-                hipLaunchKernelGGL(k_kd1_assign_acc<true>, dim3(G), dim3(F1_T), 0, c->stream, pts, n, cen, k,
-                                   it == iters - 1 ? labels : (uint32_t *)nullptr, lab8, ntiles, part, mm, bnd);
-                ST_LAUNCH_CHECK();
-            }
-            mark(c, "k1.assign");
-            KTimer kt(c, "k1.sum");
-            hipLaunchKernelGGL(k_kd1_final, dim3(k), dim3(256), 0, c->stream, part, G, k, n, cen, seq_flag, emin_c,
-                               sabs_c, cnt_c, start, fstart, ticket, dinfo, dcols, ddraws, ndraws, dstate,
-                               queued ? ff_max : 0xffffffffu, bnd, ffz);
-            ST_LAUNCH_CHECK();
-            if (queued) {
-                // the flagged path queued behind the final with no read-back: its kernels find
-                // the flagged clusters on the device and return at once when there are none
-                const unsigned gb = (unsigned)std::min<uint64_t>((nbt + 3) / 4, 2048);
-                hipLaunchKernelGGL(k_ff_batch, dim3(gb), dim3(256), 0, c->stream, lab8, pts, n, nbt, k, seq_flag,
-                                   emin_c, sabs_c, ffscr, ffagg, fflist);
-                hipLaunchKernelGGL(k_ff_bscan, dim3(FF_MAX), dim3(FN_T), 0, c->stream, nbt, fflist, ffagg, fftot);
-                const unsigned gp = (unsigned)std::min<uint64_t>(((uint64_t)FF_MAX * nbt + 3) / 4, 4096);
-                hipLaunchKernelGGL(k_ff_place, dim3(gp), dim3(256), 0, c->stream, nbt, fflist, fstart, emin_c,
-                                   sabs_c, ffscr, ffagg, ffz, vals, ffpool, ffcnt, ffpos, fftot);
-                hipLaunchKernelGGL(k_ff_finish, dim3(FF_MAX), dim3(FN_T), 0, c->stream, nbt, fflist, seq_flag,
-                                   fstart, emin_c, sabs_c, fftot, vals, ffpool, ffcnt, ffpos, cand_buf,
-                                   replay_cap(), cen, dstate);
-                ST_LAUNCH_CHECK();
-                if (getenv("ST_DEBUG")) {  // flagged clusters, their members and replay candidates
-                    uint32_t hfl[FF_MAX + 1], hz[FF_MAX];
-                    std::vector<uint32_t> f2(k), fs(k + 1);
-                    ST_HIP(hipMemcpyAsync(hfl, fflist, sizeof hfl, hipMemcpyDeviceToHost, c->stream));
-                    ST_HIP(hipMemcpyAsync(hz, ffz, sizeof hz, hipMemcpyDeviceToHost, c->stream));
-                    ST_HIP(hipMemcpyAsync(f2.data(), seq_flag, 4 * k, hipMemcpyDeviceToHost, c->stream));
-                    ST_HIP(hipMemcpyAsync(fs.data(), fstart, 4 * (k + 1), hipMemcpyDeviceToHost, c->stream));
-                    ST_HIP(hipStreamSynchronize(c->stream));
-                    fprintf(stderr, "[st k1] n=%llu flagged=%u", (unsigned long long)n, hfl[0]);
-                    for (uint32_t f = 0; f < hfl[0] && f < (uint32_t)FF_MAX; ++f)
-                        fprintf(stderr, " c%u:members=%u,cands=%u,seq=%u", hfl[1 + f],
-                                fs[hfl[1 + f] + 1] - fs[hfl[1 + f]], hz[f], f2[hfl[1 + f]] == 2u ? 1u : 0u);
-                    fprintf(stderr, "\n");
-                }
-                mark(c, "k1.update");
-                continue;
-            }
-            ST_HIP(hipMemcpyAsync(hinfo, dinfo, 8, hipMemcpyDeviceToHost, c->stream));
-            ST_HIP(hipStreamSynchronize(c->stream));
-            const uint32_t nflag = hinfo[0], ftotal = hinfo[1];
-            uint32_t nseq = 0;
-            if (nflag) {
-                // the flagged clusters' members in point order (fvals, starts fstart), then
-                // the chunked replay and, where it gives up, the sequential chain
-                if (nflag <= ff_max && !getenv("ST_K1_TILES")) {
-                    const uint32_t nch = (uint32_t)((n + FF_CH - 1) / FF_CH);
-                    hipLaunchKernelGGL(k_ff_count, dim3(G), dim3(256), 0, c->stream, lab8, n, nch, k, seq_flag, fhist);
-                    hipLaunchKernelGGL(k_ff_scan, dim3(nflag), dim3(FS_T), 0, c->stream, fhist, nch, k, seq_flag,
-                                       fstart);
-                    hipLaunchKernelGGL(k_ff_scatter, dim3(G), dim3(256), 0, c->stream, lab8, pts, n, nch, k, seq_flag,
-                                       fhist, vals);
-                } else {
-                    hipLaunchKernelGGL(k_flag_tiles, dim3(G), dim3(F1_T), 0, c->stream, lab8, n, ntiles, k, seq_flag,
-                                       fhist);
-                    hipLaunchKernelGGL(k_flag_scan, dim3(k), dim3(SC_T), 0, c->stream, fhist, ntiles, seq_flag, fstart);
-                    hipLaunchKernelGGL(k_flag_scatter, dim3(G), dim3(F1_T), 0, c->stream, lab8, pts, n, ntiles, k,
-                                       kbits, seq_flag, fhist, vals);
-                }
-                ST_LAUNCH_CHECK();
-                // short chunks: the flagged clusters are few, their replay passes run over many
-                // workgroups at once
-                const uint64_t fch = ftotal / FL_CH + nflag + 1;
-                chunk_list(c, fstart, k, ch_cnt, ch_first, chunks, nullptr, FL_CH);
-                chunked_replay(c, vals, fstart, k, fch, chunks, ch_first, seq_flag, emin_c, sabs_c, rp_csum, rp_total,
-                               rp_ccnt, rp_cof, rp_ctot, cand_buf, cen, nullptr, nullptr);
-                if (getenv("ST_DEBUG")) {
-                    std::vector<uint32_t> f2(k);
-                    ST_HIP(hipMemcpyAsync(f2.data(), seq_flag, 4 * k, hipMemcpyDeviceToHost, c->stream));
-                    ST_HIP(hipStreamSynchronize(c->stream));
-                    for (int i = 0; i < k; ++i) nseq += f2[i] == 2;
-                }
-                hipLaunchKernelGGL(k_sum1d_seq, dim3(k), dim3(64), 0, c->stream, vals, fstart, seq_flag, cen);
-                ST_LAUNCH_CHECK();
-            }
-            if (getenv("ST_DEBUG"))
-                fprintf(stderr, "[st k1] n=%llu uncertified=%u sequential-fallback=%u\n", (unsigned long long)n, nflag,
-                        nseq);
-            mark(c, "k1.update");
-        }
-        return;
-    }
+    const int kbits = label_bits(k);
+    const bool debug = getenv("ST_DEBUG") != nullptr;
     for (int it = 0; it < iters; ++it) {
-        const uint32_t *vals_s = nullptr;
-        if (fused) {
-            auto *ckeys = wsT<uint32_t>(c, "k1.ckeys", (size_t)k);
-            auto *corder = wsT<uint32_t>(c, "k1.corder", (size_t)k);
-            hipLaunchKernelGGL(k_sortkeys, dim3(grid_for(k, 256, 256)), dim3(256), 0, c->stream, cen, k, ckeys, corder);
+        const bool paired = assign1d(c, pts, n, k, cen, labels, keys, vals, it == iters - 1);
+        mark(c, "k1.assign");
+        if (!paired) {
+            hipLaunchKernelGGL(k_pairs1d, dim3(grid_for(n, 256, 8192)), dim3(256), 0, c->stream, pts, labels, n, keys,
+                               vals);
             ST_LAUNCH_CHECK();
-            radix_sort_u32(c, ckeys, corder, (uint64_t)k, 0, 32, "k1.csort");
-            {
-                KTimer kt(c, "k1.assign");
-                hipLaunchKernelGGL(k_kd1_assign_hist, dim3(ntiles), dim3(F1_T), 0, c->stream, pts, n, cen, corder, k,
-                                   it == iters - 1 ? labels : (uint32_t *)nullptr, lab8, fhist, ntiles);
-                ST_LAUNCH_CHECK();
-            }
-            mark(c, "k1.assign");
-            scan_u32(c, fhist, fhist, (uint64_t)256 * ntiles, nullptr);
-            hipLaunchKernelGGL(k_lab_scatter<uint8_t>, dim3(ntiles), dim3(F1_T), 0, c->stream, lab8, pts, n, kbits,
-                               fhist, ntiles, vals);
-            hipLaunchKernelGGL(k_f1_starts, dim3(grid_for((uint64_t)k + 1, 256, 256)), dim3(256), 0, c->stream,
-                               fhist, ntiles, k, n, start);
-            ST_LAUNCH_CHECK();
-            vals_s = vals;
-        } else {
-            const bool paired = assign1d(c, pts, n, k, cen, labels, keys, vals, it == iters - 1);
-            mark(c, "k1.assign");
-            // update
-            if (!paired) {
-                hipLaunchKernelGGL(k_pairs1d, dim3(grid_for(n, 256, 8192)), dim3(256), 0, c->stream, pts, labels, n,
-                                   keys, vals);
-                ST_LAUNCH_CHECK();
-            }
-            uint32_t *skeys = keys, *svals = vals;  // where the sort leaves its result (no copy back)
-            radix_sort_u32_inplace_or_swap(c, keys, vals, n, 0, kbits, "k1.msort", &skeys, &svals);
-            bounds_from_sorted(c, skeys, n, k, start);
-            vals_s = svals;
         }
+        uint32_t *skeys = keys, *svals = vals;  // where the sort leaves its result (no copy back)
+        radix_sort_u32_inplace_or_swap(c, keys, vals, n, 0, kbits, "k1.msort", &skeys, &svals);
+        bounds_from_sorted(c, skeys, n, k, start);
         {
             KTimer kt(c, "k1.sum");
-            {
-                const unsigned gk = grid_for((uint64_t)k, 256, 1024);
-                chunk_list(c, start, k, ch_cnt, ch_first, chunks, acc);
-                hipLaunchKernelGGL(k_sum1d_chunks, dim3(maxch), dim3(SC_T), 0, c->stream, vals_s, chunks, ch_first + k,
-                                   acc);
-                hipLaunchKernelGGL(k_sum1d_final, dim3(gk), dim3(256), 0, c->stream, acc, start, k, cen, seq_flag,
-                                   emin_c, sabs_c);
-                ST_LAUNCH_CHECK();
-            }
-            std::vector<uint32_t> f1;
-            if (getenv("ST_DEBUG")) {
-                ST_HIP(hipStreamSynchronize(c->stream));
-                f1.resize(k);
-                ST_HIP(hipMemcpy(f1.data(), seq_flag, 4 * k, hipMemcpyDeviceToHost));
-            }
-            chunked_replay(c, vals_s, start, k, maxch, chunks, ch_first, seq_flag, emin_c, sabs_c, rp_csum, rp_total,
+            chunk_list(c, start, k, ch_cnt, ch_first, chunks, acc);
+            hipLaunchKernelGGL(k_sum1d_chunks, dim3(maxch), dim3(SC_T), 0, c->stream, svals, chunks, ch_first + k, acc);
+            hipLaunchKernelGGL(k_sum1d_final, dim3(grid_for((uint64_t)k, 256, 1024)), dim3(256), 0, c->stream, acc,
+                               start, k, cen, seq_flag, emin_c, sabs_c);
+            ST_LAUNCH_CHECK();
+            const uint32_t nflag = debug ? count_flag(c, seq_flag, k, 1u) : 0u;
+            chunked_replay(c, svals, start, k, maxch, chunks, ch_first, seq_flag, emin_c, sabs_c, rp_csum, rp_total,
                            rp_ccnt, rp_cof, rp_ctot, cand_buf, cen, nullptr, nullptr);
-            if (getenv("ST_DEBUG")) {
-                ST_HIP(hipStreamSynchronize(c->stream));
-                std::vector<uint32_t> f2(k);
-                ST_HIP(hipMemcpy(f2.data(), seq_flag, 4 * k, hipMemcpyDeviceToHost));
-                int a = 0, b = 0;
-                for (int i = 0; i < k; ++i) {
-                    a += f1[i] == 1;
-                    b += f2[i] == 2;
-                }
-                fprintf(stderr, "[st k1] n=%llu uncertified=%d sequential-fallback=%d\n", (unsigned long long)n, a, b);
-            }
-            hipLaunchKernelGGL(k_sum1d_seq, dim3(k), dim3(64), 0, c->stream, vals_s, start, seq_flag, cen);
+            if (debug)
+                fprintf(stderr, "[st k1] n=%llu uncertified=%u sequential-fallback=%u\n", (unsigned long long)n, nflag,
+                        count_flag(c, seq_flag, k, 2u));
+            hipLaunchKernelGGL(k_sum1d_seq, dim3(k), dim3(64), 0, c->stream, svals, start, seq_flag, cen);
             ST_LAUNCH_CHECK();
         }
         reseed_empty(c, dcols, 1, n, k, start, ddraws, ndraws, dstate, cen);
         mark(c, "k1.update");
     }
+}
+
+}  // namespace
+
+// The two iterations and the inputs that take them: k <= 256, cluster1d's codebooks, the
+// accumulating one; everything else the general one.  ST_K1_SORT=1 (test hook) sends k <= 256
+// to the general iteration too.
+void kmeans1d_loop(st_ctx *c, const float *pts, const float *const *dcols, uint64_t n, int k, int iters,
+                   const double *ddraws, uint64_t ndraws, State *dstate, float *cen, uint32_t *labels) {
+    if (k <= 256 && n > 0 && n < (1ull << 32) && !getenv("ST_K1_SORT"))
+        k1_accumulating(c, pts, dcols, n, k, iters, ddraws, ndraws, dstate, cen, labels);
+    else
+        k1_general(c, pts, dcols, n, k, iters, ddraws, ndraws, dstate, cen, labels);
 }
 
 // the sharded 1-D member order: a stable sort by (segment, label) is a stable sort by label inside
@@ -2152,8 +2085,7 @@ void kmeans1d_loop(st_ctx *c, const float *pts, const float *const *dcols, uint6
 void seg_label_sort1d(st_ctx *c, const float *pts, const uint32_t *labels, uint64_t n, int nseg, int k,
                       uint32_t *vals, uint32_t *start) {
     const uint64_t ns = n / (uint64_t)nseg;
-    int kbits = 1;
-    while ((1 << kbits) < k) ++kbits;
+    const int kbits = label_bits(k);
     const uint32_t ntiles = (uint32_t)((ns + F1_TILE - 1) / F1_TILE);
     auto *hist = wsT<uint32_t>(c, "k1.shist", (size_t)256 * (ntiles ? ntiles : 1));
     for (int sg = 0; sg < nseg; ++sg) {
@@ -2161,7 +2093,7 @@ void seg_label_sort1d(st_ctx *c, const float *pts, const uint32_t *labels, uint6
         if (ns) {
             hipLaunchKernelGGL(k_lab_hist, dim3(ntiles), dim3(F1_T), 0, c->stream, labels + o, ns, hist, ntiles);
             scan_u32(c, hist, hist, (uint64_t)256 * ntiles, nullptr);
-            hipLaunchKernelGGL(k_lab_scatter<uint32_t>, dim3(ntiles), dim3(F1_T), 0, c->stream, labels + o, pts + o, ns,
+            hipLaunchKernelGGL(k_lab_scatter, dim3(ntiles), dim3(F1_T), 0, c->stream, labels + o, pts + o, ns,
                                kbits, hist, ntiles, vals + o);
             hipLaunchKernelGGL(k_f1_starts, dim3(grid_for((uint64_t)k + 1, 256, 256)), dim3(256), 0, c->stream, hist,
                                ntiles, k, ns, start + (uint64_t)sg * k, (uint32_t)o);

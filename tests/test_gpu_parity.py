@@ -183,6 +183,34 @@ def test_kmeans_vs_oracle(ctx, n, d, k, iters, dist):
         assert st['pairs'] + st['ambiguous'] <= st['points']
 
 
+@pytest.mark.parametrize('n,k,tiny_frac', [(20_000, 257, 0.0), (20_000, 257, 0.02), (20_000, 4096, 0.02),
+                                           (20_000, 4097, 0.02), (600_000, 300, 0.02)])
+def test_kmeans_1d_general_vs_oracle(ctx, n, k, tiny_frac, monkeypatch, capfd):
+    """The general 1-D iteration (k > 256): assign, (label, value) pairs, radix sort, chunked
+    sums, replay and re-seeding.  k = 257 is its smallest k; 4096 is the most centroids the
+    LDS assign takes and 4097 the global-memory one; at 600,000 points the cluster around 0
+    holds 16,726 members, five 4,096-member chunks.  Tiny members (x 1e-9) next to ordinary
+    ones in one cluster cannot pass the exactness certificate: ST_DEBUG's counts show that a
+    sum was replayed."""
+    uncertified = tiny_frac > 0 and k <= 300
+    if uncertified:
+        monkeypatch.setenv('ST_DEBUG', '1')
+        capfd.readouterr()
+    rng = np.random.default_rng(n + k)
+    col = rng.normal(0, 1, n).astype(np.float32)
+    col[rng.random(n) < tiny_frac] *= np.float32(1e-9)
+    draws = oracle.mulberry32(n + k, 4 * k * 4 + 64)
+    cent, labels, used = ctx.kmeans([col], k, 3, draws)
+    if uncertified:
+        import re
+        err = capfd.readouterr().err
+        assert sum(int(x) for x in re.findall(r'uncertified=(\d+)', err)) >= 1, err[-2000:]
+    rc, ocent, olabels, oused = oracle.kmeans([col], k, 3, draws)
+    assert rc == 0 and used == oused
+    same_bits(labels, olabels)
+    same_bits(cent, ocent)
+
+
 @pytest.mark.parametrize('n,d,k,iters,dist,split,chunk', [(20_000, 45, 1024, 3, 'gauss', 4, 16),
                                                          (20_000, 45, 1024, 3, 't3', 1, 1),
                                                          (30_000, 24, 2048, 2, 'gauss', 8, 5),
@@ -223,9 +251,11 @@ def test_cluster1d_uncertified_sums_vs_oracle(ctx, tiny_frac, mode, monkeypatch,
     (the sequential fallback).  mode: the iteration queued without read-backs, the flagged
     clusters updated by the three-pass flagged update (default); the flagged count read back
     each iteration (ST_K1_SYNC), the flagged clusters' members gathered by the tile kernels (ST_K1_TILES),
-    every iteration's member sort (ST_K1_SORT), the queued run abandoned at the first flagged
-    cluster and rerun synchronised (ST_K1_FF_MAX=0), or the replay capped at 0 / 2 candidates so
-    that the sequential chain takes over (ST_REPLAY_CAP; ST_DEBUG's counts show that it did)."""
+    the general iteration that k > 256 takes -- assign, pairs, radix sort, chunked sums -- over
+    the 900k values with no, a few and many uncertified sums (ST_K1_SORT), the queued run
+    abandoned at the first flagged cluster and rerun synchronised (ST_K1_FF_MAX=0), or the
+    replay capped at 0 / 2 candidates so that the sequential chain takes over (ST_REPLAY_CAP;
+    ST_DEBUG's counts show that it did)."""
     set_mode(monkeypatch, mode)
     capped = mode.startswith('ST_REPLAY_CAP') and (tiny_frac > 0 if mode.endswith('=0') else tiny_frac >= 0.02)
     if capped:
