@@ -570,6 +570,47 @@ int st_dev_decompress_ply(st_ctx *ctx, uint64_t n, const float *const *chunk, co
 int st_decompress_ply(st_ctx *ctx, uint64_t n, const float *const *chunk, const uint32_t *const *vertex,
                       const uint8_t *const *sh, int32_t nsh, float *const *out);
 
+/* ---- the PLY writer (writers/write-ply.ts, the 'ply' case of index.ts:126-133) ----
+ * st_ply_header_text (host only, no context): the header text of write-ply.ts:19-35 for one
+ * element -- "ply", "format binary_little_endian 1.0", a "comment <c>" line per comment, "element
+ * <element> <t->n>" (element NULL = "vertex"), a "property <type> <name>" line per column with
+ * the type names of write-ply.ts:5-16 (char uchar short ushort int uint float double),
+ * "end_header"; every line ends in '\n'.  Only t's n, names and types are read.
+ * st_ply_element_text: the "element ..." and "property ..." lines alone, for a host that composes
+ * a header of several elements.  Both results are malloc'd (st_free); *size excludes the NUL.
+ * st_dev_ply_rows: the kernel alone, the inverse of st_dev_ply_transpose -- rows [row0, row0 +
+ * nrows) of a device table of any column types as nrows x R row-major bytes (write-ply.ts:54-62:
+ * the columns' elements back to back in column order, no padding) at dev_rows (device, 4-byte
+ * aligned), on the context stream.  Columns are aligned to their type.  R > 12 KiB returns
+ * ST_ERR_UNSUPPORTED; zero rows or zero columns is a no-op.
+ * st_dev_ply_rows_file / st_ply_rows_file: all rows of a device / host table (uploaded once)
+ * written to out_fd at its current position, the rows only.  They are interleaved a piece at a
+ * time into a small device staging buffer and come down through st_compressed_ply_file's pinned
+ * slots while a host thread writes the slot before; the n x R bytes never exist in HBM at once.
+ * out_fd as for st_compressed_ply_file: seekable, open for writing, not O_APPEND (ST_ERR_ARG
+ * before any work); its position ends after the output and a longer file is cut there.
+ * st_ply_file: processDataTable on a host table, then header + rows (one element named "vertex",
+ * the CLI's shape); the columns and their order are the processed table's.  *out_m = its rows,
+ * *size = the bytes written.
+ * st_ply_ply_file: the CLI's `in.ply [actions] out.ply` -- the element's rows go from the file
+ * into HBM (st_dev_ply_read), stay resident through the actions and the interleave, and only the
+ * output's bytes cross back.  element < 0 selects the element named "vertex".
+ * One device writes: the st_set_devices group is not used by these calls.
+ * One divergence from the reference: write-ply.ts:40 wraps a column's whole ArrayBuffer, so a
+ * column that is an offset view would be written from its buffer's start; here a column's own
+ * elements are written. */
+int st_ply_header_text(const st_ttable *t, const char *element, const char *const *comments, int32_t ncomments,
+                       char **out, uint64_t *size);
+int st_ply_element_text(const st_ttable *t, const char *element, char **out, uint64_t *size);
+int st_dev_ply_rows(st_ctx *ctx, const st_ttable *dev_table, uint64_t row0, uint64_t nrows, uint8_t *dev_rows);
+int st_dev_ply_rows_file(st_ctx *ctx, const st_ttable *dev_table, int32_t out_fd, uint64_t *size);
+int st_ply_rows_file(st_ctx *ctx, const st_ttable *host_table, int32_t out_fd, uint64_t *size);
+int st_ply_file(st_ctx *ctx, const st_ttable *src, const st_action *actions, int32_t nactions,
+                const char *const *comments, int32_t ncomments, int32_t out_fd, uint64_t *out_m, uint64_t *size);
+int st_ply_ply_file(st_ctx *ctx, int32_t fd, const st_ply_header *h, int32_t element, const st_action *actions,
+                    int32_t nactions, const char *const *comments, int32_t ncomments, int32_t out_fd,
+                    uint64_t *out_m, uint64_t *size);
+
 /* ---- the other input formats: .splat, .ksplat, .spz (index.ts:52-76) ----------
  * Each reader decodes packed per-splat records into 14 + nsh float32 columns in its own order:
  * x y z scale_0..2 f_dc_0..2 opacity rot_0..3 f_rest_0..nsh-1 (nsh = 0, 9, 24 or 45).

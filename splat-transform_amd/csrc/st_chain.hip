@@ -251,36 +251,17 @@ std::string compressed_ply_header(uint64_t m, int C, const char *version) {
     return h + "end_header\n";
 }
 
-// the device arrays to fd at offsets from its position: pinned slots filled by device-to-host copies on
-// the context's stream while a host thread writes the slot before (ext4 / xfs serialise buffered
-// writes to one file, so one writer); the file ends at the last byte
-uint64_t compressed_ply_to_file(st_ctx *c, uint64_t m, int C, const float *dchunk, const uint32_t *dvert,
-                                const uint8_t *dsh, int fd, const char *version) {
-    const std::string head = compressed_ply_header(m, C, version);
-    // from the descriptor's position, as the reference's FileHandle.write calls go (the CLI's
-    // fresh output: 0), which is left at the end of what was written
-    const off_t pos = lseek(fd, 0, SEEK_CUR);
-    ST_REQUIRE(pos >= 0, ST_ERR_ARG, "compressed ply file: the descriptor has no position");
-    const uint64_t base = (uint64_t)pos;
-    write_at(fd, reinterpret_cast<const uint8_t *>(head.data()), head.size(), base);
-    const uint64_t nch = (m + 255) / 256;
-    struct Region {
-        const uint8_t *dev;
-        uint64_t bytes, off;
-    };
-    std::vector<Region> rs;
-    uint64_t off = base + head.size();
-    for (const Region &r : {Region{reinterpret_cast<const uint8_t *>(dchunk), nch * 72, 0},
-                            Region{reinterpret_cast<const uint8_t *>(dvert), m * 16, 0},
-                            Region{dsh, C ? m * 3 * (uint64_t)C : 0, 0}}) {
-        if (r.bytes) rs.push_back({r.dev, r.bytes, off});
-        off += r.bytes;
-    }
-    const uint64_t total = off;
-    constexpr int SLOTS = 4;
+// device bytes on their way into a file: pinned slots filled by device-to-host copies on the
+// context's stream while a host thread writes the slot before (ext4 / xfs serialise buffered
+// writes to one file, so one writer).  next() hands out the next slot once the writer is done with
+// it; the caller queues a copy into it and submit()s it with its file offset; finish() waits for
+// the writer and rethrows its error.  ST_CPF_SLOT_MB: the slot size (32 MiB).
+struct FileRing {
+    static constexpr int SLOTS = 4;
+    st_ctx *c;
+    int fd;
     uint64_t slot = 32ull << 20;
-    if (const char *e = std::getenv("ST_CPF_SLOT_MB")) slot = std::max<uint64_t>(1, std::strtoull(e, nullptr, 10)) << 20;
-    auto *ring = static_cast<uint8_t *>(pinned_slot(c, "cpf.ring", SLOTS * slot));
+    uint8_t *ring;
     struct Piece {
         int s;
         uint64_t bytes, off;
@@ -291,7 +272,14 @@ uint64_t compressed_ply_to_file(st_ctx *c, uint64_t m, int C, const float *dchun
     std::deque<Piece> q;
     bool busy[SLOTS] = {}, fin = false;
     std::exception_ptr err;
-    std::thread writer([&] {
+    std::thread writer;
+    int k = 0, cur = -1;
+    FileRing(st_ctx *ctx, int f) : c(ctx), fd(f) {
+        if (const char *e = std::getenv("ST_CPF_SLOT_MB")) slot = std::max<uint64_t>(1, std::strtoull(e, nullptr, 10)) << 20;
+        ring = static_cast<uint8_t *>(pinned_slot(c, "cpf.ring", SLOTS * slot));
+        writer = std::thread([this] { loop(); });
+    }
+    void loop() {
         for (;;) {
             Piece p;
             {
@@ -321,47 +309,138 @@ uint64_t compressed_ply_to_file(st_ctx *c, uint64_t m, int C, const float *dchun
             }
             cv.notify_all();
         }
-    });
-    auto stop = [&] {
+    }
+    // the next pinned slot, free to be copied into; null after an error (finish() rethrows it)
+    uint8_t *next() {
+        cur = k++ % SLOTS;
+        std::unique_lock<std::mutex> lk(mu);
+        cv.wait(lk, [&] { return !busy[cur] || err; });
+        if (err) return nullptr;
+        busy[cur] = true;
+        return ring + cur * slot;
+    }
+    // what the stream holds so far fills the slot of the last next(): its `bytes` go to file offset off
+    void submit(uint64_t bytes, uint64_t off) {
+        hipEvent_t ev;
+        ST_HIP(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+        const hipError_t e = hipEventRecord(ev, c->stream);
+        if (e != hipSuccess) (void)hipEventDestroy(ev);
+        ST_HIP(e);
+        {
+            std::lock_guard<std::mutex> lk(mu);
+            q.push_back({cur, bytes, off, ev});
+        }
+        cv.notify_all();
+    }
+    void fail(std::exception_ptr e) {
+        std::lock_guard<std::mutex> lk(mu);
+        if (!err) err = e;
+    }
+    void stop() {
         {
             std::lock_guard<std::mutex> lk(mu);
             fin = true;
         }
         cv.notify_all();
         if (writer.joinable()) writer.join();
+    }
+    void finish() {
+        stop();
+        if (err) std::rethrow_exception(err);
+    }
+    ~FileRing() { stop(); }
+};
+
+// the output's first byte: the descriptor's position, as the reference's FileHandle.write calls go
+// (the CLI's fresh output: 0)
+uint64_t file_base(int fd, const char *what) {
+    const off_t pos = lseek(fd, 0, SEEK_CUR);
+    ST_REQUIRE(pos >= 0, ST_ERR_ARG, std::string(what) + ": the descriptor has no position");
+    return (uint64_t)pos;
+}
+
+// the file ends at the output's last byte, and the position is left there
+void file_end(int fd, uint64_t total, const char *what) {
+    sog_file_truncate(fd, total);
+    ST_REQUIRE(lseek(fd, (off_t)total, SEEK_SET) == (off_t)total, ST_ERR_ARG, std::string(what) + ": lseek failed");
+}
+
+// the device arrays to fd at offsets from its position through the ring; the file ends at the last byte
+uint64_t compressed_ply_to_file(st_ctx *c, uint64_t m, int C, const float *dchunk, const uint32_t *dvert,
+                                const uint8_t *dsh, int fd, const char *version) {
+    const std::string head = compressed_ply_header(m, C, version);
+    const uint64_t base = file_base(fd, "compressed ply file");
+    write_at(fd, reinterpret_cast<const uint8_t *>(head.data()), head.size(), base);
+    const uint64_t nch = (m + 255) / 256;
+    struct Region {
+        const uint8_t *dev;
+        uint64_t bytes, off;
     };
+    std::vector<Region> rs;
+    uint64_t off = base + head.size();
+    for (const Region &r : {Region{reinterpret_cast<const uint8_t *>(dchunk), nch * 72, 0},
+                            Region{reinterpret_cast<const uint8_t *>(dvert), m * 16, 0},
+                            Region{dsh, C ? m * 3 * (uint64_t)C : 0, 0}}) {
+        if (r.bytes) rs.push_back({r.dev, r.bytes, off});
+        off += r.bytes;
+    }
+    const uint64_t total = off;
+    FileRing ring(c, fd);
     try {
-        int k = 0;
-        for (const Region &r : rs)
-            for (uint64_t o = 0; o < r.bytes; o += slot, ++k) {
-                const int sidx = k % SLOTS;
-                const uint64_t nb = std::min(slot, r.bytes - o);
-                {
-                    std::unique_lock<std::mutex> lk(mu);
-                    cv.wait(lk, [&] { return !busy[sidx] || err; });
-                    if (err) break;
-                    busy[sidx] = true;
-                }
-                hipEvent_t ev;
-                ST_HIP(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-                ST_HIP(hipMemcpyAsync(ring + sidx * slot, r.dev + o, nb, hipMemcpyDeviceToHost, c->stream));
-                ST_HIP(hipEventRecord(ev, c->stream));
-                {
-                    std::lock_guard<std::mutex> lk(mu);
-                    q.push_back({sidx, nb, r.off + o, ev});
-                }
-                cv.notify_all();
+        bool ok = true;
+        for (size_t i = 0; i < rs.size() && ok; ++i)
+            for (uint64_t o = 0; o < rs[i].bytes && ok; o += ring.slot) {
+                const uint64_t nb = std::min(ring.slot, rs[i].bytes - o);
+                uint8_t *host = ring.next();
+                if (!(ok = host != nullptr)) break;
+                ST_HIP(hipMemcpyAsync(host, rs[i].dev + o, nb, hipMemcpyDeviceToHost, c->stream));
+                ring.submit(nb, rs[i].off + o);
             }
     } catch (...) {
-        {
-            std::lock_guard<std::mutex> lk(mu);
-            if (!err) err = std::current_exception();
-        }
+        ring.fail(std::current_exception());
     }
-    stop();
-    if (err) std::rethrow_exception(err);
-    sog_file_truncate(fd, total);
-    ST_REQUIRE(lseek(fd, (off_t)total, SEEK_SET) == (off_t)total, ST_ERR_ARG, "compressed ply file: lseek failed");
+    ring.finish();
+    file_end(fd, total, "compressed ply file");
+    return total - base;
+}
+
+// writePly's rows (write-ply.ts:37-67) of a device table to fd at file offset `off`: rows are
+// interleaved piece by piece (whole workgroups of rows, one ring slot each) into two device staging
+// buffers and come down through the ring -- the m * R bytes never exist in HBM at once.  Returns
+// the bytes written.
+uint64_t ply_rows_to_file(st_ctx *c, const st_ttable *t, int fd, uint64_t off) {
+    PlyRows pr(c, t, "plyw");
+    if (!t->n || !pr.R) return 0;
+    FileRing ring(c, fd);
+    const uint64_t per = (uint64_t)pr.RB * pr.R;  // <= 48 KiB
+    const uint64_t piece_rows = std::max<uint64_t>(1, ring.slot / per) * pr.RB;
+    uint8_t *stage[2] = {wsT<uint8_t>(c, "plyw.stage0", piece_rows * pr.R), wsT<uint8_t>(c, "plyw.stage1", piece_rows * pr.R)};
+    try {
+        int k = 0;
+        for (uint64_t row = 0; row < t->n; row += piece_rows, ++k) {
+            const uint64_t nr = std::min(piece_rows, t->n - row), nb = nr * pr.R;
+            uint8_t *host = ring.next();
+            if (!host) break;
+            pr.run(row, nr, stage[k & 1]);
+            ST_HIP(hipMemcpyAsync(host, stage[k & 1], nb, hipMemcpyDeviceToHost, c->stream));
+            ring.submit(nb, off + row * pr.R);
+        }
+    } catch (...) {
+        ring.fail(std::current_exception());
+    }
+    ring.finish();
+    return t->n * pr.R;
+}
+
+// header + rows of the chain's table to out_fd from its position (writePly with one element named
+// "vertex", index.ts:126-133)
+uint64_t ply_chain_to_file(Chain &ch, const char *const *comments, int ncomments, int fd) {
+    const st_ttable *t = ch.typed();
+    const std::string head = ply_header_text(t, "vertex", comments, ncomments, false);
+    const uint64_t base = file_base(fd, "ply file");
+    write_at(fd, reinterpret_cast<const uint8_t *>(head.data()), head.size(), base);
+    const uint64_t total = base + head.size() + ply_rows_to_file(ch.c, t, fd, base + head.size());
+    file_end(fd, total, "ply file");
     return total - base;
 }
 
@@ -593,6 +672,64 @@ int st_compressed_ply_file(st_ctx *c, const st_ttable *src, const st_action *act
         *size = compressed_ply_to_file(c, m, C, dchunk, dvert, dsh, out_fd, version);
         *out_m = m;
         *out_sh_coeffs = C;
+    });
+}
+
+int st_dev_ply_rows_file(st_ctx *c, const st_ttable *t, int32_t out_fd, uint64_t *size) {
+    return guard([&] {
+        ST_REQUIRE(c && t && size, ST_ERR_ARG, "NULL argument");
+        check_src(t);
+        sog_file_check(out_fd);
+        use_device(c);
+        const uint64_t base = file_base(out_fd, "ply file");
+        *size = ply_rows_to_file(c, t, out_fd, base);
+        file_end(out_fd, base + *size, "ply file");
+    });
+}
+
+int st_ply_rows_file(st_ctx *c, const st_ttable *src, int32_t out_fd, uint64_t *size) {
+    return guard([&] {
+        ST_REQUIRE(c && src && size, ST_ERR_ARG, "NULL argument");
+        check_src(src);
+        sog_file_check(out_fd);
+        use_device(c);
+        Chain ch{c};
+        upload_chain(c, src, ch);
+        const uint64_t base = file_base(out_fd, "ply file");
+        *size = ply_rows_to_file(c, ch.typed(), out_fd, base);
+        file_end(out_fd, base + *size, "ply file");
+    });
+}
+
+int st_ply_file(st_ctx *c, const st_ttable *src, const st_action *actions, int32_t nactions,
+                const char *const *comments, int32_t ncomments, int32_t out_fd, uint64_t *out_m, uint64_t *size) {
+    return guard([&] {
+        ST_REQUIRE(c && src && out_m && size && (actions || nactions == 0), ST_ERR_ARG, "NULL argument");
+        ST_REQUIRE(ncomments >= 0 && (comments || ncomments == 0), ST_ERR_ARG, "ply file: NULL comments");
+        check_src(src);
+        sog_file_check(out_fd);
+        use_device(c);
+        Chain ch{c};
+        upload_chain(c, src, ch);
+        run_actions(ch, actions, nactions);
+        *size = ply_chain_to_file(ch, comments, ncomments, out_fd);
+        *out_m = ch.n;
+    });
+}
+
+int st_ply_ply_file(st_ctx *c, int32_t fd, const st_ply_header *h, int32_t element, const st_action *actions,
+                    int32_t nactions, const char *const *comments, int32_t ncomments, int32_t out_fd,
+                    uint64_t *out_m, uint64_t *size) {
+    return guard([&] {
+        ST_REQUIRE(c && h && fd >= 0 && out_m && size && (actions || nactions == 0), ST_ERR_ARG, "NULL argument");
+        ST_REQUIRE(ncomments >= 0 && (comments || ncomments == 0), ST_ERR_ARG, "ply file: NULL comments");
+        sog_file_check(out_fd);
+        use_device(c);
+        Chain ch{c};
+        ply_chain(c, fd, h, element, ch);
+        run_actions(ch, actions, nactions);
+        *size = ply_chain_to_file(ch, comments, ncomments, out_fd);
+        *out_m = ch.n;
     });
 }
 

@@ -405,6 +405,23 @@ void materialize_lazy(st_ctx *c, const void *const *host, int n);
 void drop_mirrors_locked(st_ctx *c, const std::function<bool(const st_ctx::HostMirror &)> &pick);
 void decompress_ply_dev(st_ctx *c, uint64_t n, const float *const *chunk, const uint32_t *const *vertex,
                         const uint8_t *const *sh, int nsh, float *const *out);
+// the PLY writer (write-ply.ts): k_ply_rows over one device table, the inverse of the reader's
+// transpose.  The constructor checks the table (ST_ERR_ARG for a bad type or a misaligned column,
+// ST_ERR_UNSUPPORTED for rows longer than 12 KiB) and uploads its layout once; run() queues rows
+// [row0, row0 + nrows) as nrows x R bytes at out (4-byte aligned, device) on the context stream
+struct PlyRows {
+    st_ctx *c;
+    uint32_t R = 0, RB = 64;  // row bytes, rows per workgroup
+    int ncol = 0;
+    void *d_props = nullptr;
+    void **d_cols = nullptr;
+    PlyRows(st_ctx *ctx, const st_ttable *t, const std::string &tag);
+    void run(uint64_t row0, uint64_t nrows, uint8_t *out);
+};
+// write-ply.ts:19-35 for one element ("vertex" when element is null): the whole header, or only the
+// element / property lines
+std::string ply_header_text(const st_ttable *t, const char *element, const char *const *comments, int ncomments,
+                            bool element_only);
 
 // multi-GPU building blocks (st_dist.hip)
 void minmax_dev(st_ctx *c, const float *const *cols, int ncols, uint64_t n, double *lo, double *hi);

@@ -1,5 +1,5 @@
-// st_ply.hip -- PLY ingest and the compressed-PLY reader on the device (SURVEY.md 8f
-// ranks 2 and 4).
+// st_ply.hip -- PLY ingest, the compressed-PLY reader and the PLY writer's interleave on the
+// device.
 //
 //   header         readers/read-ply.ts:111-137 (search for "\nend_header\n" within
 //                  128 KiB), parseHeader :54-110 (host; same accepted grammar and errors)
@@ -14,6 +14,11 @@
 //   decompress     readers/decompress-ply.ts:82-232: one thread per splat, f64 JS
 //                  semantics (lerp, unorm unpacking, Math.sqrt, V8's Math.log), f32
 //                  stores; SH bytes -> floats.                   read 16 B + D, write 56 + 4D B
+//   writer         writers/write-ply.ts:18-68: the header text (host) and k_ply_rows, the
+//                  transpose's inverse -- one thread per (column, row) loads the value
+//                  (coalesced) into the row's LDS image, the block's rows leave as coalesced
+//                  4-byte stores.  HBM traffic 2 x row bytes per row.  The file forms are in
+//                  st_chain.hip.
 #include <fcntl.h>
 #include <unistd.h>
 
@@ -217,6 +222,56 @@ struct Transposer {
     }
 };
 
+// a value's bytes at LDS address a, by the widest store the address allows
+__device__ inline void lds_put(uint8_t *lds8, uint32_t a, uint64_t v, uint32_t size) {
+    if (size == 8 && !(a & 7)) {
+        *(uint64_t *)(lds8 + a) = v;
+    } else if (size >= 4 && !(a & 3)) {
+        *(uint32_t *)(lds8 + a) = (uint32_t)v;
+        if (size == 8) *(uint32_t *)(lds8 + a + 4) = (uint32_t)(v >> 32);
+    } else if (size >= 2 && !(a & 1)) {
+        for (uint32_t k = 0; k < size; k += 2) *(uint16_t *)(lds8 + a + k) = (uint16_t)(v >> (8 * k));
+    } else {
+        for (uint32_t k = 0; k < size; ++k) lds8[a + k] = (uint8_t)(v >> (8 * k));
+    }
+}
+
+// rows [row0, row0 + nrows) of the columns -> nrows x R bytes at out (write-ply.ts:54-62): the
+// inverse of k_ply_cols.  One thread per (column, row) loads the value (consecutive threads =
+// consecutive rows of one column: coalesced) and puts it at the field's offset in the row's LDS
+// image, the images R bytes apart as in the output; then the block's nr * R bytes leave LDS as
+// coalesced 4-byte stores, a partial last word byte by byte.
+__global__ __launch_bounds__(512) void k_ply_rows(const void *const *__restrict__ cols,
+                                                  const PropSlot *__restrict__ props, int nprops, uint64_t row0,
+                                                  uint64_t nrows, uint32_t R, uint32_t RB,
+                                                  uint8_t *__restrict__ out) {
+    extern __shared__ uint32_t lds32[];
+    uint8_t *lds8 = (uint8_t *)lds32;
+    const uint64_t r0 = (uint64_t)blockIdx.x * RB;
+    const uint32_t nr = (uint32_t)((nrows - r0) < RB ? (nrows - r0) : RB);
+    const uint32_t total = nr * (uint32_t)nprops;
+    for (uint32_t e = threadIdx.x; e < total; e += blockDim.x) {
+        const uint32_t p = e / nr, r = e - p * nr;
+        const PropSlot ps = props[p];
+        const uint64_t row = row0 + r0 + r;
+        uint64_t v;
+        switch (ps.size) {
+            case 1: v = ((const uint8_t *)cols[p])[row]; break;
+            case 2: v = ((const uint16_t *)cols[p])[row]; break;
+            case 4: v = ((const uint32_t *)cols[p])[row]; break;
+            default: v = ((const uint64_t *)cols[p])[row]; break;
+        }
+        lds_put(lds8, r * R + ps.offset, v, ps.size);
+    }
+    __syncthreads();
+    // RB is a multiple of 4, so every block's bytes start 4-byte aligned in out
+    const uint32_t bytes = nr * R, words = bytes / 4;
+    uint8_t *dst8 = out + r0 * R;
+    uint32_t *dst = (uint32_t *)dst8;
+    for (uint32_t i = threadIdx.x; i < words; i += blockDim.x) dst[i] = lds32[i];
+    if (threadIdx.x < (bytes & 3)) dst8[words * 4 + threadIdx.x] = lds8[words * 4 + threadIdx.x];
+}
+
 // ---- compressed PLY -------------------------------------------------------------
 struct DecompArgs {
     const float *chunk[18];
@@ -307,6 +362,66 @@ void decompress_ply_dev(st_ctx *c, uint64_t n, const float *const *chunk, const 
         hipLaunchKernelGGL(k_decompress_sh, dim3(grid_for(n, 256)), dim3(256), 0, c->stream, S, nsh, n);
         ST_LAUNCH_CHECK();
     }
+}
+
+PlyRows::PlyRows(st_ctx *ctx, const st_ttable *t, const std::string &tag) : c(ctx) {
+    ST_REQUIRE(t->ncol >= 0 && (t->ncol == 0 || (t->types && t->cols)), ST_ERR_ARG, "ply rows: bad table");
+    ncol = t->ncol;
+    std::vector<PropSlot> ps(ncol);
+    uint64_t off = 0;
+    for (int p = 0; p < ncol; ++p) {
+        const uint32_t z = (uint32_t)type_size(t->types[p]);
+        ST_REQUIRE(z > 0, ST_ERR_ARG, "ply rows: bad column type");
+        ST_REQUIRE(t->n == 0 || t->cols[p], ST_ERR_ARG, "ply rows: NULL column");
+        ST_REQUIRE(((uintptr_t)t->cols[p] & (z - 1)) == 0, ST_ERR_ARG, "ply rows: misaligned column");
+        ps[p] = {(uint32_t)off, z};
+        off += z;
+        ST_REQUIRE(off <= LDS_ROWS_BYTES / 4, ST_ERR_UNSUPPORTED, "ply: rows longer than 12 KiB");
+    }
+    R = (uint32_t)off;
+    if (R) RB = std::min(256u, (LDS_ROWS_BYTES / R) & ~3u);
+    d_props = wsT<PropSlot>(c, tag + ".props", ncol ? ncol : 1);
+    d_cols = wsT<void *>(c, tag + ".cols", ncol ? ncol : 1);
+    if (ncol) {
+        ST_HIP(hipMemcpyAsync(d_props, ps.data(), sizeof(PropSlot) * ncol, hipMemcpyHostToDevice, c->stream));
+        ST_HIP(hipMemcpyAsync(d_cols, t->cols, sizeof(void *) * ncol, hipMemcpyHostToDevice, c->stream));
+    }
+}
+
+void PlyRows::run(uint64_t row0, uint64_t nrows, uint8_t *out) {
+    if (!nrows || !R) return;
+    KTimer kt(c, "ply.rows");
+    // six resident workgroups of 256 threads (24 of a CU's 32 wave slots) keep enough loads in
+    // flight; an LDS image above 160 KiB / 6 admits fewer, and 512 threads put the idle slots to
+    // work (measured: DESIGN.md, "the PLY writer")
+    const unsigned threads = (uint64_t)RB * R > 160 * 1024 / 6 ? 512 : 256;
+    hipLaunchKernelGGL(k_ply_rows, dim3((unsigned)((nrows + RB - 1) / RB)), dim3(threads), (RB * R + 3) & ~3u,
+                       c->stream, (const void *const *)d_cols, (const PropSlot *)d_props, ncol, row0, nrows, R, RB, out);
+    ST_LAUNCH_CHECK();
+}
+
+std::string ply_header_text(const st_ttable *t, const char *element, const char *const *comments, int ncomments,
+                            bool element_only) {
+    // columnTypeToPlyType (write-ply.ts:5-16) in ST_PLY_* order
+    static const char *names[] = {"char", "uchar", "short", "ushort", "int", "uint", "float", "double"};
+    ST_REQUIRE(t->ncol >= 0 && (t->ncol == 0 || (t->names && t->types)), ST_ERR_ARG, "ply header: bad table");
+    ST_REQUIRE(ncomments >= 0 && (comments || ncomments == 0), ST_ERR_ARG, "ply header: NULL comments");
+    std::string h;
+    if (!element_only) {
+        h = "ply\nformat binary_little_endian 1.0\n";
+        for (int i = 0; i < ncomments; ++i) {
+            ST_REQUIRE(comments[i], ST_ERR_ARG, "ply header: NULL comment");
+            h += std::string("comment ") + comments[i] + "\n";
+        }
+    }
+    h += std::string("element ") + (element ? element : "vertex") + " " + std::to_string(t->n) + "\n";
+    for (int p = 0; p < t->ncol; ++p) {
+        ST_REQUIRE(type_size(t->types[p]) > 0, ST_ERR_ARG, "ply header: bad column type");
+        ST_REQUIRE(t->names[p], ST_ERR_ARG, "ply header: NULL column name");
+        h += std::string("property ") + names[t->types[p] - ST_PLY_CHAR] + " " + t->names[p] + "\n";
+    }
+    if (!element_only) h += "end_header\n";
+    return h;
 }
 
 // one element of a PLY file (fd) into device columns, streamed through pinned chunks; a sink
@@ -818,6 +933,40 @@ int st_dev_ply_transpose(st_ctx *c, const st_ply_header *h, int32_t element, con
         use_device(c);
         Transposer tp(c, h->elements[element], cols, "plyt");
         tp.run(rows, nrows, 0);
+    });
+}
+
+static int header_text_out(const st_ttable *t, const char *element, const char *const *comments, int32_t ncomments,
+                           bool element_only, char **out, uint64_t *size) {
+    return guard([&] {
+        ST_REQUIRE(t && out && size, ST_ERR_ARG, "NULL argument");
+        const std::string h = ply_header_text(t, element, comments, ncomments, element_only);
+        char *p = static_cast<char *>(std::malloc(h.size() + 1));
+        ST_REQUIRE(p, ST_ERR_NOMEM, "ply header: allocation failed");
+        std::memcpy(p, h.c_str(), h.size() + 1);
+        *out = p;
+        *size = h.size();
+    });
+}
+
+int st_ply_header_text(const st_ttable *t, const char *element, const char *const *comments, int32_t ncomments,
+                       char **out, uint64_t *size) {
+    return header_text_out(t, element, comments, ncomments, false, out, size);
+}
+
+int st_ply_element_text(const st_ttable *t, const char *element, char **out, uint64_t *size) {
+    return header_text_out(t, element, nullptr, 0, true, out, size);
+}
+
+int st_dev_ply_rows(st_ctx *c, const st_ttable *t, uint64_t row0, uint64_t nrows, uint8_t *dev_rows) {
+    return guard([&] {
+        ST_REQUIRE(c && t, ST_ERR_ARG, "NULL argument");
+        ST_REQUIRE(row0 <= t->n && nrows <= t->n - row0, ST_ERR_ARG, "ply rows: rows outside the table");
+        use_device(c);
+        PlyRows pr(c, t, "plyr");
+        if (!nrows || !pr.R) return;
+        ST_REQUIRE(dev_rows && ((uintptr_t)dev_rows & 3) == 0, ST_ERR_ARG, "ply rows: output must be 4-byte aligned");
+        pr.run(row0, nrows, dev_rows);
     });
 }
 

@@ -124,6 +124,8 @@ EXPORTS = [
     'st_splat_layout', 'st_ksplat_layout', 'st_spz_layout', 'st_dev_splat_decode', 'st_dev_ksplat_decode',
     'st_dev_spz_decode', 'st_splat_read', 'st_dev_splat_read', 'st_ksplat_read', 'st_dev_ksplat_read', 'st_spz_read',
     'st_dev_spz_read',
+    'st_ply_header_text', 'st_ply_element_text', 'st_dev_ply_rows', 'st_dev_ply_rows_file', 'st_ply_rows_file',
+    'st_ply_file', 'st_ply_ply_file',
 ]
 
 
@@ -518,6 +520,56 @@ def ply_parse_header(data):
     buf = ctypes.create_string_buffer(bytes(data), len(data))
     check(lib().st_ply_parse_header(buf, ctypes.c_uint64(len(data)), ctypes.byref(h)))
     return h
+
+
+def _schema_ttable(schema, n):
+    """st_ttable of names and types only (st_ply_header_text reads nothing else): schema is a list of
+    (name, numpy dtype or array)"""
+    names = [k for k, _ in schema]
+    c_names = (ctypes.c_char_p * max(len(names), 1))(*[k.encode() for k in names])
+    c_types = (ctypes.c_int32 * max(len(names), 1))(
+        *[ply_type_of(a) if hasattr(a, 'data_ptr') or isinstance(a, np.ndarray) else _NP_TO_PLY[np.dtype(a)]
+          for _, a in schema])
+    t = TTable(n, len(names), ctypes.cast(c_names, ctypes.POINTER(ctypes.c_char_p)),
+               ctypes.cast(c_types, ctypes.POINTER(ctypes.c_int32)), None)
+    t._keep = (c_names, c_types)
+    return t
+
+
+def _comments_arg(comments):
+    keep = [c.encode() for c in comments]
+    return (ctypes.c_char_p * max(len(keep), 1))(*keep), ctypes.c_int32(len(keep))
+
+
+def ply_header_text(schema, n, element=None, comments=(), element_only=False):
+    """writePly's header text (write-ply.ts:19-35) for one element of n rows: schema is a list of
+    (name, numpy dtype or array); element None = 'vertex'.  element_only: the element / property
+    lines alone (st_ply_element_text), for headers of several elements.  Host only -> bytes"""
+    t = _schema_ttable(schema, n)
+    out, size = ctypes.c_void_p(), ctypes.c_uint64(0)
+    el = element.encode() if element is not None else None
+    if element_only:
+        check(lib().st_ply_element_text(ctypes.byref(t), el, ctypes.byref(out), ctypes.byref(size)))
+    else:
+        cs, nc = _comments_arg(comments)
+        check(lib().st_ply_header_text(ctypes.byref(t), el, cs, nc, ctypes.byref(out), ctypes.byref(size)))
+    return _take(out, size)
+
+
+class _OutFd:
+    """a path (opened for writing without O_TRUNC: the library cuts the file) or a descriptor of the
+    caller's"""
+
+    def __init__(self, out):
+        self.own = not isinstance(out, int)
+        self.fd = os.open(out, os.O_WRONLY | os.O_CREAT, 0o644) if self.own else out
+
+    def __enter__(self):
+        return ctypes.c_int32(self.fd)
+
+    def __exit__(self, *exc):
+        if self.own:
+            os.close(self.fd)
 
 
 READER_COLS = ['x', 'y', 'z', 'scale_0', 'scale_1', 'scale_2', 'f_dc_0', 'f_dc_1', 'f_dc_2', 'opacity',
@@ -1232,6 +1284,84 @@ class Context:
         finally:
             os.close(ofd)
         return m.value, C.value, size.value
+
+    # ---- writePly (write-ply.ts) ---------------------------------------------------------
+    def dev_ply_rows(self, cols, out, row0=0, nrows=None):
+        """st_dev_ply_rows: rows [row0, row0 + nrows) of device columns (list of (name, tensor) or a
+        dict, any types) interleaved into `out`, a device uint8 tensor of >= nrows * row bytes"""
+        t = make_ttable(cols)
+        if nrows is None:
+            nrows = t.n - row0
+        check(lib().st_dev_ply_rows(self.h, ctypes.byref(t), ctypes.c_uint64(row0), ctypes.c_uint64(nrows),
+                                    _ptr(out)))
+
+    def ply_rows_file(self, cols, out):
+        """the rows alone of a table (numpy columns: st_ply_rows_file, uploaded once; torch tensors:
+        st_dev_ply_rows_file) written at the position of `out`, a descriptor or a path -> bytes written"""
+        t = make_ttable(cols)
+        dev = t.ncol and hasattr(t._keep[3][0][1], 'data_ptr')
+        size = ctypes.c_uint64()
+        with _OutFd(out) as fd:
+            check((lib().st_dev_ply_rows_file if dev else lib().st_ply_rows_file)(self.h, ctypes.byref(t), fd,
+                                                                                 ctypes.byref(size)))
+        return size.value
+
+    def dev_ply_file(self, elements, out, comments=()):
+        """writePly (write-ply.ts:18-68) of tables already in HBM: elements is a list of (element name,
+        columns) -- or (element name, columns, rows) for an element without columns -- or the columns
+        of one 'vertex' element (list of (name, tensor) or a dict); the header is composed here and
+        each element's rows stream down through st_dev_ply_rows_file.  `out`: a path or a descriptor
+        (written from its position) -> bytes written"""
+        if isinstance(elements, dict) or (elements and not isinstance(elements[0][1], (dict, list, tuple))):
+            elements = [('vertex', elements)]
+        tables = [(e[0], make_ttable(e[1], e[2] if len(e) > 2 else None)) for e in elements]
+        head = b'ply\nformat binary_little_endian 1.0\n' + b''.join(b'comment %s\n' % c.encode() for c in comments)
+        for e, (name, t) in zip(elements, tables):
+            items = list(e[1].items()) if isinstance(e[1], dict) else list(e[1])
+            head += ply_header_text(items, t.n, name, element_only=True)
+        head += b'end_header\n'
+        with _OutFd(out) as fd:
+            total = len(head)
+            pos = os.lseek(fd.value, 0, os.SEEK_CUR)
+            os.pwrite(fd.value, head, pos)
+            os.lseek(fd.value, pos + total, os.SEEK_SET)
+            for _, t in tables:
+                size = ctypes.c_uint64()
+                check(lib().st_dev_ply_rows_file(self.h, ctypes.byref(t), fd, ctypes.byref(size)))
+                total += size.value
+        return total
+
+    def ply_file(self, cols, actions, out, comments=()):
+        """processDataTable + writePly of a host table (list of (name, numpy array) or a dict) into
+        `out`, a path or a descriptor (st_ply_file): (rows written, file bytes).  The input arrays are
+        not changed"""
+        items = list(cols.items()) if isinstance(cols, dict) else list(cols)
+        ts = make_ttable(items, len(items[0][1]) if items else 0)
+        acts = make_actions(actions)
+        cs, nc = _comments_arg(comments)
+        m, size = ctypes.c_uint64(), ctypes.c_uint64()
+        with _OutFd(out) as fd:
+            check(lib().st_ply_file(self.h, ctypes.byref(ts), acts, ctypes.c_int32(len(actions)), cs, nc, fd,
+                                    ctypes.byref(m), ctypes.byref(size)))
+        return m.value, size.value
+
+    def ply_ply_file(self, path, actions, out, comments=(), element=-1):
+        """the CLI's `in.ply [actions] out.ply` (st_ply_ply_file): the element's rows stay in HBM from
+        ingest to output: (rows written, file bytes)"""
+        fd = os.open(path, os.O_RDONLY)
+        try:
+            h = PlyHeader()
+            check(lib().st_ply_read_header(ctypes.c_int32(fd), ctypes.byref(h)))
+            acts = make_actions(actions)
+            cs, nc = _comments_arg(comments)
+            m, size = ctypes.c_uint64(), ctypes.c_uint64()
+            with _OutFd(out) as ofd:
+                check(lib().st_ply_ply_file(self.h, ctypes.c_int32(fd), ctypes.byref(h), ctypes.c_int32(element), acts,
+                                            ctypes.c_int32(len(actions)), cs, nc, ofd, ctypes.byref(m),
+                                            ctypes.byref(size)))
+        finally:
+            os.close(fd)
+        return m.value, size.value
 
     def ply_sog_bundle(self, path, actions, iters, draws, dos_time, dos_date, element=-1):
         """readPly + processDataTable + writeSog to .sog bytes from the file (st_ply_sog_bundle):
