@@ -71,8 +71,8 @@ void kmeans1d_loop(st_ctx *c, const float *pts, const float *const *dcols, uint6
                    const double *ddraws, uint64_t ndraws, km::State *dstate, float *cen, uint32_t *labels);
 // (sum64: host array of device float64 columns whose values calcAverage sums instead of the
 // float32 points -- the JS numbers of columns that are not float32)
-void kmeansnd_loop(st_ctx *c, const float *const *cols, const float *const *dcols, int d, uint64_t n, int k,
-                   int iters, const double *ddraws, uint64_t ndraws, km::State *dstate, float *cen, uint32_t *labels,
+void kmeansnd_loop(st_ctx *c, const float *const *dcols, int d, uint64_t n, int k, int iters, const double *ddraws,
+                   uint64_t ndraws, km::State *dstate, float *cen, uint32_t *labels,
                    const double *const *sum64 = nullptr);
 
 // step form of the loops (shared with the distributed step API, st_dist.hip)

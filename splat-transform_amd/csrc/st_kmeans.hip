@@ -529,7 +529,7 @@ uint64_t kmeans_dev(st_ctx *c, const float *const *cols, int d, uint64_t n, int 
     if (d == 1)
         kmeans1d_loop(c, cols[0], dcols, n, k, iters, ddraws, ndraws, dstate, cen, labels);
     else
-        kmeansnd_loop(c, cols, dcols, d, n, k, iters, ddraws, ndraws, dstate, cen, labels, sum64);
+        kmeansnd_loop(c, dcols, d, n, k, iters, ddraws, ndraws, dstate, cen, labels, sum64);
 
     ST_HIP(hipMemcpyAsync(&hs, dstate, sizeof(State), hipMemcpyDeviceToHost, c->stream));
     ST_HIP(hipStreamSynchronize(c->stream));

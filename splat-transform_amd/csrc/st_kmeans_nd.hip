@@ -2067,16 +2067,19 @@ void big_sums(st_ctx *c, const T *aos, int d, uint64_t n, int k, const uint32_t 
     ST_LAUNCH_CHECK();
 }
 
+// the clusters' sums over their sorted members: one wave each up to sumnd_big() members, the huge
+// ones (a cluster of the table's all-zero rows) sliced over the chip (big_sums); every cluster,
+// or the `rows` listed in only (their count on the device: nonly)
 template <typename T>
 void launch_sums(st_ctx *c, const T *aos, int d, uint64_t n, int k, const uint32_t *members, const uint32_t *start,
-                 float *cen) {
+                 float *cen, const uint32_t *only = nullptr, const uint32_t *nonly = nullptr, uint32_t rows = 0) {
     const uint32_t big = sumnd_big();
     const uint32_t cap = (uint32_t)(n / ((uint64_t)big + 1) + 1);
     auto *list = wsT<uint32_t>(c, "kn.blist", cap);
     auto *nlist = wsT<uint32_t>(c, "kn.bn", 1);
     ST_HIP(hipMemsetAsync(nlist, 0, 4, c->stream));
-    hipLaunchKernelGGL(k_sumnd<T>, dim3((k + 3) / 4), dim3(256), 0, c->stream, aos, d, members, start, k, cen, big,
-                       cap, list, nlist, (const uint32_t *)nullptr, (const uint32_t *)nullptr);
+    hipLaunchKernelGGL(k_sumnd<T>, dim3(((only ? rows : k) + 3) / 4), dim3(256), 0, c->stream, aos, d, members, start,
+                       k, cen, big, cap, list, nlist, only, nonly);
     if (n > big) big_sums(c, aos, d, n, k, members, start, cen, cap, list, nlist);
     ST_LAUNCH_CHECK();
 }
@@ -2141,6 +2144,23 @@ bool probe_denorm(st_ctx *c) {
         case 4: { constexpr int KS = 4; CALL; } break; \
         default: throw Error(ST_ERR_UNSUPPORTED, "kmeans: dimension too large for the MFMA assign (D <= 61)"); \
     }
+// the SH palettes' row widths (aos_ld of d = 45 / 24 / 9) as the constant LD of a launch; the
+// callers have checked palette_ld(), or run only after a fused fix-up, which implies it
+#define ST_LD_DISPATCH(LDV, ...)                               \
+    switch (LDV) {                                             \
+        case 48: { constexpr int LD = 48; __VA_ARGS__; } break; \
+        case 24: { constexpr int LD = 24; __VA_ARGS__; } break; \
+        default: { constexpr int LD = 12; __VA_ARGS__; } break; \
+    }
+// the palettes' d as the constant DT of a launch (0: any other d, read at run time)
+#define ST_DT_DISPATCH(DV, ...)                                \
+    switch (DV) {                                              \
+        case 45: { constexpr int DT = 45; __VA_ARGS__; } break; \
+        case 24: { constexpr int DT = 24; __VA_ARGS__; } break; \
+        case 9: { constexpr int DT = 9; __VA_ARGS__; } break;   \
+        default: { constexpr int DT = 0; __VA_ARGS__; } break;  \
+    }
+static bool palette_ld(int ld) { return ld == 48 || ld == 24 || ld == 12; }
 
 // ---- steps: prepare the point set once, then one exact assign per iteration -------
 void nd_prepare(st_ctx *c, const float *const *dcols, int d, uint64_t n) {
@@ -2167,18 +2187,8 @@ void nd_prepare(st_ctx *c, const float *const *dcols, int d, uint64_t n) {
     float sigma = 1.0f;
     if (amax > 0) sigma = std::ldexp(1.0f, -std::ilogb(amax));
     const dim3 gpf((unsigned)(((uint64_t)ntiles * 32 + PF_PTS - 1) / PF_PTS));
-    if (d == 45)
-        hipLaunchKernelGGL(k_point_frags<45>, gpf, dim3(PF_PTS), 0, c->stream, dcols, d, n, ntiles, ks, sigma, pfrag,
-                           pnorm, pdn, aos);
-    else if (d == 24)
-        hipLaunchKernelGGL(k_point_frags<24>, gpf, dim3(PF_PTS), 0, c->stream, dcols, d, n, ntiles, ks, sigma, pfrag,
-                           pnorm, pdn, aos);
-    else if (d == 9)
-        hipLaunchKernelGGL(k_point_frags<9>, gpf, dim3(PF_PTS), 0, c->stream, dcols, d, n, ntiles, ks, sigma, pfrag,
-                           pnorm, pdn, aos);
-    else
-        hipLaunchKernelGGL(k_point_frags<0>, gpf, dim3(PF_PTS), 0, c->stream, dcols, d, n, ntiles, ks, sigma, pfrag,
-                           pnorm, pdn, aos);
+    ST_DT_DISPATCH(d, hipLaunchKernelGGL(k_point_frags<DT>, gpf, dim3(PF_PTS), 0, c->stream, dcols, d, n, ntiles, ks,
+                                         sigma, pfrag, pnorm, pdn, aos));
     ST_LAUNCH_CHECK();
     c->kn_sigma = sigma;
     c->kn_n = n;
@@ -2196,8 +2206,333 @@ __global__ __launch_bounds__(256) void k_rows_aos(const float *__restrict__ cen,
     }
 }
 
-uint32_t nd_assign_core(st_ctx *c, const float *const *dcols, int d, uint64_t n, int k, const float *cen,
-                        uint32_t *labels, km::State *dstate, bool walk_ties, NdFused *fz = nullptr);
+// ---- the exact assign against k centroids, phase by phase (nd_assign_core runs them in order) ----
+
+// what the phases share, from the first six (Assign{c, d, n, k, labels, dstate}): the shape, the
+// prepared points (nd_prepare), the centroids' forms (prepare_centroids), the sweep's lists
+struct Assign {
+    st_ctx *c;
+    int d;
+    uint64_t n;
+    int k;
+    uint32_t *labels;
+    State *dstate;
+    int ld = aos_ld(d), ks = kp_of(d) / 16;
+    uint32_t ntiles = (uint32_t)((n + 31) / 32);
+    // centroid tiles, padded to whole LDS stages with rows that can never win (k_centroid_frags)
+    uint32_t ctiles = (uint32_t)(((k + 31) / 32 + CT_STAGE - 1) / CT_STAGE * CT_STAGE);
+    uint32_t ncodes = ctiles * 2;  // tile-halves
+    Bound bnd = make_bound(d, probe_denorm(c));
+    const uint4 *pfrag = wsT<uint4>(c, "kn.pfrag", (size_t)ntiles * ks * 64);
+    const float *pnorm = wsT<float>(c, "kn.pnorm", n);
+    const float *pdn = wsT<float>(c, "kn.pdn", n);
+    const float *aos = wsT<float>(c, "kn.aos", n * (size_t)ld);
+    uint32_t *scal = wsT<uint32_t>(c, "kn.scal", 4);  // [1]=cmax bits [2]=max residual norm bits
+    uint4 *cfrag = wsT<uint4>(c, "kn.cfrag", (size_t)ctiles * ks * 64);
+    float *thr = wsT<float>(c, "kn.thr", n);
+    uint32_t *amb = wsT<uint32_t>(c, "kn.amb", n);
+    uint32_t *ties = wsT<uint32_t>(c, "kn.ties", n);
+    float *caos = wsT<float>(c, "kn.caos", (size_t)k * ld);
+    float2 *cfix = wsT<float2>(c, "kn.cfix", (size_t)ctiles * 32 * (ld / 2));
+    float *cnorm = wsT<float>(c, "kn.cnorm", (size_t)ctiles * 32);
+    float *chalf = wsT<float>(c, "kn.chalf", (size_t)ctiles * 2);
+    float *cdn = wsT<float>(c, "kn.cdn", (size_t)ctiles * 32);
+    float *chalf_d = wsT<float>(c, "kn.chalfd", (size_t)ctiles * 2);
+    float *ntab = wsT<float>(c, "kn.ntab", NTAB);
+    uint32_t *pair_pts = wsT<uint32_t>(c, "kn.pairpts", n);
+    uint2 *pair_codes = wsT<uint2>(c, "kn.paircodes", n);
+};
+
+// the centroids' MFMA fragments, row-major copies and norm tables
+void prepare_centroids(st_ctx *c, const Assign &a, const float *cen) {
+    ST_HIP(hipMemsetAsync(a.scal + 1, 0, 8, c->stream));
+    ST_REQUIRE(a.ks <= CF_W, ST_ERR_INTERNAL, "kmeans: more fragments per row than centroid waves");
+    hipLaunchKernelGGL(k_centroid_frags, dim3(grid_for((uint64_t)a.ctiles * 32, 64, 4096)), dim3(64 * CF_W), 0,
+                       c->stream, cen, a.d, a.k, a.ctiles, a.ks, c->kn_sigma, a.cfrag, a.scal + 1, a.caos, a.cfix,
+                       a.cnorm, a.cdn);
+    hipLaunchKernelGGL(k_half_max, dim3(grid_for((uint64_t)a.ctiles * 2, 256, 1024)), dim3(256), 0, c->stream, a.cnorm,
+                       a.cdn, a.ctiles * 2, a.chalf, a.chalf_d);
+    hipLaunchKernelGGL(k_norm_table, dim3(1), dim3(NTAB), 0, c->stream, a.cnorm, a.cdn, a.ctiles * 32, a.scal + 1,
+                       a.ntab);
+    ST_LAUNCH_CHECK();
+}
+
+// the fused fix-up's slices of decided points: k_fixrow_lp writes their partial sums, the fused
+// update (nd_fused_update, nd_fused_partials) reads them -- one block per name, so one size
+struct FusedWs {  // FusedWs{c, n, ld, ncodes}
+    st_ctx *c;
+    uint64_t n;
+    int ld;
+    uint32_t ncodes;
+    uint64_t slices = ncodes + n / FA_SL + 1;  // bound: a last partial one per code and the whole ones
+    uint32_t *soff = wsT<uint32_t>(c, "kn.fasoff", (size_t)ncodes + 1);
+    double *psum = wsT<double>(c, "kn.fasum", slices * 16 * ld);
+    double *pabs = wsT<double>(c, "kn.faabs", slices * 16 * ld);
+    int *pemin = wsT<int>(c, "kn.faemin", slices * 16 * ld);
+    uint32_t *pcnt = wsT<uint32_t>(c, "kn.facnt", slices * 16);
+};
+
+// the decided points grouped by tile-half code from the codes' starts (cursor): points alone
+// (uint32_t) or (point, code) pairs (uint2)
+template <typename G>
+void group_by_code(st_ctx *c, const uint32_t *labels, uint64_t n, uint32_t ncodes, uint32_t *cursor, G *grouped) {
+    // workgroups of the one-reservation grouping (0: k_code_scatter's 4,096-point rounds), read
+    // per call so tests can set it around one call; k_code_scatter_run reads the labels 16 bytes
+    // at a time: a caller's unaligned labels take the rounds
+    const char *e = getenv("ST_CS_WG");
+    const int cs_wg = ((uintptr_t)labels & 15u) ? 0 : e ? atoi(e) : 256;
+    if (cs_wg > 0)
+        hipLaunchKernelGGL(k_code_scatter_run<G>, dim3(grid_for(n, 256, (unsigned)cs_wg)), dim3(256), 0, c->stream,
+                           labels, (uint32_t)n, ncodes, cursor, grouped);
+    else
+        hipLaunchKernelGGL(k_code_scatter<G>, dim3(grid_for(n, FB_TILE, 2048)), dim3(256), 0, c->stream, labels,
+                           (uint32_t)n, ncodes, cursor, grouped);
+    ST_LAUNCH_CHECK();
+}
+
+// The decided points' fix-up behind the sweep.  hist (the sweep's count per tile-half code) given:
+// the points are grouped by code and settled with register-resident rows, fused with their sums
+// (k_fixrow_lp, sets fz->valid / ncodes) when the caller wants those, else k_fixrow_b; ev_grp is
+// recorded once the grouping has read every label.  No hist: k_fixrow over the points in place.
+void fix_decided(st_ctx *c, const Assign &a, uint32_t *hist, NdFused *fz, bool walk_ties, hipEvent_t ev_grp) {
+    KTimer kt(c, "kn.fixrow");
+    const uint64_t n = a.n;
+    if (!hist) {
+        hipLaunchKernelGGL(k_fixrow, dim3((unsigned)((n * 16 + 255) / 256)), dim3(256), 0, c->stream, a.aos, a.d,
+                           a.cfix, a.caos, a.k, (uint32_t)n, a.labels, a.ties, a.dstate);
+        ST_LAUNCH_CHECK();
+        return;
+    }
+    auto *cursor = wsT<uint32_t>(c, "kn.fbcur", a.ncodes);
+    auto *ndec = wsT<uint32_t>(c, "kn.fbnd", 1);
+    // k_fixrow_lp sums DT = 45 / 24 / 9 dimensions of its LD-wide rows (the SH palettes' d):
+    // any other d in the same row width (10-12, 21-23, 46-48) takes the member-sort update
+    const bool fused = fz && fz->want && walk_ties && (a.d == 45 || a.d == 24 || a.d == 9);
+    if (fused) {
+        // the grouped points alone (a slice knows its code); slice offsets and the codes' starts in
+        // one workgroup
+        auto *grouped = wsT<uint32_t>(c, "kn.fbpts1", n);
+        const FusedWs f{c, n, a.ld, a.ncodes};
+        hipLaunchKernelGGL(k_fa_slices, dim3(1), dim3(FS_T), 0, c->stream, hist, a.ncodes, f.soff, cursor, ndec);
+        group_by_code(c, a.labels, n, a.ncodes, cursor, grouped);
+        ST_HIP(hipEventRecord(ev_grp, c->stream));
+        // the slices (their count is on the device) shared out over up to 4,096 workgroups: about
+        // one slice each at the palette shapes (1,024 stay resident; at 2,048 -- two slices per
+        // workgroup in two rounds -- the launch took 5% longer, 850 against 812 us at 10M x 45)
+        const dim3 gl((unsigned)std::min<uint64_t>(f.slices, 4096));
+        ST_LD_DISPATCH(a.ld, hipLaunchKernelGGL(k_fixrow_lp<LD>, gl, dim3(64 * FL_WAVES), 0, c->stream, a.aos, a.d,
+                                                a.caos, a.k, grouped, hist, cursor, f.soff, a.ncodes, a.labels,
+                                                a.ties, a.dstate, f.psum, f.pabs, f.pemin, f.pcnt));
+        fz->valid = true;
+        fz->ncodes = a.ncodes;
+    } else {
+        auto *grouped = wsT<uint2>(c, "kn.fbpts2", n);  // (point, code) pairs
+        scan_u32(c, hist, cursor, a.ncodes, ndec);
+        group_by_code(c, a.labels, n, a.ncodes, cursor, grouped);
+        ST_HIP(hipEventRecord(ev_grp, c->stream));
+        const dim3 g((unsigned)(((n + FB_RUN - 1) / FB_RUN * 16 + 255) / 256));
+        ST_LD_DISPATCH(a.ld, hipLaunchKernelGGL(k_fixrow_b<LD>, g, dim3(256), 0, c->stream, a.aos, a.d, a.caos, a.k,
+                                                grouped, ndec, a.labels, a.ties, a.dstate));
+    }
+    ST_LAUNCH_CHECK();
+}
+
+// where the pair and ambiguous points' fix-ups run and list their ties: the context's stream, the
+// assign's counters and tie list -- or, overlapping the decided points' fix-up, the side stream
+// with counters and a list of their own
+struct Side {
+    hipStream_t fs;
+    State *ds;     // device counters
+    uint32_t *tl;  // tie list
+    State *hs;     // host copy of ds
+    void read_back() const {  // hs = the counters behind what is queued on fs (a host sync)
+        ST_HIP(hipMemcpyAsync(hs, ds, sizeof(State), hipMemcpyDeviceToHost, fs));
+        ST_HIP(hipStreamSynchronize(fs));
+    }
+};
+
+void fix_pairs(st_ctx *c, const Assign &a, const Side &s, uint32_t npair) {
+    KTimer kt(c, "kn.fixpair", s.fs);
+    const dim3 g((npair * 32 + 255) / 256);
+    if (palette_ld(a.ld)) {
+        ST_LD_DISPATCH(a.ld, hipLaunchKernelGGL(k_fixpair_b<LD>, g, dim3(256), 0, s.fs, a.aos, a.d, a.cfix, a.caos,
+                                                a.k, a.pair_pts, a.pair_codes, npair, a.labels, s.tl, s.ds));
+    } else {
+        hipLaunchKernelGGL(k_fixpair, g, dim3(256), 0, s.fs, a.aos, a.d, a.cfix, a.caos, a.k, a.pair_pts,
+                           a.pair_codes, npair, a.labels, s.tl, s.ds);
+    }
+    ST_LAUNCH_CHECK();
+}
+
+// points whose window holds more than CAND_CAP rows (wide windows: outlying points of
+// heavy-tailed data): collected again with lists of CAND_CAP2, in batches; only those
+// that overflow these too take the KdTree walk
+void collect_overflows(st_ctx *c, const Assign &a, const Side &s, const uint32_t *ovf, uint32_t nov) {
+    const uint32_t batch = std::min(nov, (uint32_t)OVF_BATCH);
+    const uint32_t btiles = (batch + 31) / 32;
+    auto *afrag2 = wsT<uint4>(c, "kn.afrag2", (size_t)btiles * a.ks * 64);
+    auto *thr2 = wsT<float>(c, "kn.thrslot2", (size_t)btiles * 32);
+    auto *cnt2 = wsT<uint32_t>(c, "kn.ccnt2", (size_t)btiles * 32);
+    auto *cand2 = wsT<uint32_t>(c, "kn.cand2", (size_t)batch * CAND_CAP2);
+    for (uint32_t b0 = 0; b0 < nov; b0 += batch) {
+        const uint32_t m = std::min(batch, nov - b0), mt = (m + 31) / 32;
+        hipLaunchKernelGGL(k_gather_amb, dim3(grid_for((uint64_t)mt * 32, 256, 4096)), dim3(256), 0, s.fs, a.pfrag,
+                           ovf + b0, a.thr, m, a.ks, afrag2, thr2, cnt2);
+        ST_LAUNCH_CHECK();
+        ST_KS_DISPATCH(a.ks, (Sweep<KS>::collect(c, afrag2, mt, m, a.cfrag, a.ctiles, a.bnd, thr2, cnt2, cand2,
+                                                 (uint32_t)CAND_CAP2, s.fs)));
+        KTimer kt(c, "kn.exact", s.fs);
+        hipLaunchKernelGGL(k_exact, dim3((m + 3) / 4), dim3(256), 0, s.fs, a.aos, a.d, a.caos, a.k, ovf + b0, m, cnt2,
+                           cand2, (uint32_t)CAND_CAP2, a.labels, s.tl, (uint32_t *)nullptr, s.ds);
+        ST_LAUNCH_CHECK();
+    }
+    s.read_back();
+}
+
+// the ambiguous points: their candidates collected, then the exact distances; s.hs holds the
+// side's counters on return.  Returns the first lists that overflowed (collected again with
+// CAND_CAP2).
+uint32_t fix_ambiguous(st_ctx *c, const Assign &a, const Side &s, uint32_t namb) {
+    const uint32_t atiles = (namb + 31) / 32;
+    auto *afrag = wsT<uint4>(c, "kn.afrag", (size_t)atiles * a.ks * 64);
+    auto *thr_slot = wsT<float>(c, "kn.thrslot", (size_t)atiles * 32);
+    auto *cand_cnt = wsT<uint32_t>(c, "kn.ccnt", (size_t)atiles * 32);
+    auto *cand = wsT<uint32_t>(c, "kn.cand", (size_t)namb * CAND_CAP);
+    hipLaunchKernelGGL(k_gather_amb, dim3(grid_for((uint64_t)atiles * 32, 256, 4096)), dim3(256), 0, s.fs, a.pfrag,
+                       a.amb, a.thr, namb, a.ks, afrag, thr_slot, cand_cnt);
+    ST_LAUNCH_CHECK();
+    auto *ovf = wsT<uint32_t>(c, "kn.ovf", namb);
+    ST_KS_DISPATCH(a.ks, (Sweep<KS>::collect(c, afrag, atiles, namb, a.cfrag, a.ctiles, a.bnd, thr_slot, cand_cnt, cand,
+                                             (uint32_t)CAND_CAP, s.fs)));
+    {
+        KTimer kt(c, "kn.exact", s.fs);
+        hipLaunchKernelGGL(k_exact, dim3((namb + 3) / 4), dim3(256), 0, s.fs, a.aos, a.d, a.caos, a.k, a.amb, namb,
+                           cand_cnt, cand, (uint32_t)CAND_CAP, a.labels, s.tl, ovf, s.ds);
+        ST_LAUNCH_CHECK();
+    }
+    s.read_back();
+    const uint32_t ovf1 = s.hs->overflow;
+    if (ovf1) collect_overflows(c, a, s, ovf, ovf1);
+    if (getenv("ST_DEBUG")) {  // candidate-count histogram of the ambiguous points
+        std::vector<uint32_t> cc(namb);
+        ST_HIP(hipMemcpy(cc.data(), cand_cnt, namb * 4, hipMemcpyDeviceToHost));
+        uint64_t hist[6] = {0, 0, 0, 0, 0, 0};
+        for (uint32_t v : cc) ++hist[v < 5 ? v : 5];
+        fprintf(stderr, "[st kmeans] candidates per ambiguous point: 0:%llu 1:%llu 2:%llu 3:%llu 4:%llu 5+:%llu\n",
+                (unsigned long long)hist[0], (unsigned long long)hist[1], (unsigned long long)hist[2],
+                (unsigned long long)hist[3], (unsigned long long)hist[4], (unsigned long long)hist[5]);
+    }
+    return ovf1;
+}
+
+// One tie list (kn.ties) and one host copy of the counters (h) for the statistics and the tie
+// walk, in the order one stream gives: the decided points' fix-up's ties (h_fix: the sweep's
+// counts and those ties) first, then the side fix-ups'.
+// Overlap: the side stream kept a list and counters of its own (s.tl, s.ds, s.hs): its ties are
+// appended behind the fix-up's on the context's stream, and its overflow count is the assign's.
+// Serial: s.hs == h, s.ds == dstate and s.tl == kn.ties -- the side fix-ups ran behind the fix-up
+// on the one stream, appended to the one list and counted in dstate, and their last read-back left
+// the totals in h; when there were none, h still holds the sweep's read-back and takes h_fix.
+void join_ties(st_ctx *c, const Assign &a, bool overlap, const Side &s, bool side_ran, const State *h_fix, State *h,
+               hipEvent_t ev_side) {
+    if (overlap) {
+        ST_HIP(hipEventRecord(ev_side, s.fs));
+        ST_HIP(hipStreamWaitEvent(c->stream, ev_side, 0));
+        if (s.hs->ties)
+            ST_HIP(hipMemcpyAsync(a.ties + h_fix->ties, s.tl, (size_t)s.hs->ties * sizeof(uint32_t),
+                                  hipMemcpyDeviceToDevice, c->stream));
+        *h = *h_fix;
+        h->ties = h_fix->ties + s.hs->ties;
+        h->overflow = s.hs->overflow;
+    } else if (!side_ran) {
+        *h = *h_fix;
+    }
+}
+
+// the exact assign against the k centroids cen; exact ties go to the KdTree walk over these
+// centroids (walk_ties) or are left listed in kn.ties for the caller: returns their count
+uint32_t nd_assign_core(st_ctx *c, int d, uint64_t n, int k, const float *cen, uint32_t *labels, State *dstate,
+                        bool walk_ties, NdFused *fz = nullptr) {
+    ST_REQUIRE(c->kn_n == n && c->kn_d == d, ST_ERR_ARG, "kmeans assign: point set not prepared");
+    ST_REQUIRE(k <= (1 << 24), ST_ERR_UNSUPPORTED, "kmeans: K too large");
+    const Assign a{c, d, n, k, labels, dstate};
+    auto *h = static_cast<State *>(pinned(c, sizeof(State)));
+    prepare_centroids(c, a, cen);
+    ST_HIP(hipMemsetAsync(&dstate->amb, 0, 16, c->stream));  // amb + ties + overflow + pairs
+    // decided points grouped by tile-half for k_fixrow_b: the sweep counts them per code
+    const bool grouped_fix = a.ncodes <= (uint32_t)FB_MAX_CODES && palette_ld(a.ld) && !getenv("ST_FIXROW_L2");
+    auto *hist = grouped_fix ? wsT<uint32_t>(c, "kn.fbhist", a.ncodes) : nullptr;
+    if (hist) ST_HIP(hipMemsetAsync(hist, 0, a.ncodes * sizeof(uint32_t), c->stream));
+    ST_KS_DISPATCH(a.ks, (Sweep<KS>::main(c, a.pfrag, a.ntiles, (uint32_t)n, a.cfrag, a.ctiles, a.pnorm, a.pdn,
+                                          a.scal + 1, a.chalf, a.chalf_d, a.ntab, a.bnd, labels, a.thr, a.amb, dstate,
+                                          a.pair_pts, a.pair_codes, hist)));
+    // the sweep's pair / ambiguous counts are final here (the fix-up only adds ties): read back
+    // behind the sweep, waited for while the fix-up runs, so that the pairs' and the ambiguous
+    // points' kernels queue up behind it with no idle gap; the fix-up's own tie count (h_fix)
+    // is read behind it and waited for only where it is needed
+    auto *h_fix = static_cast<State *>(pinned_slot(c, "kn.hfix", sizeof(State)));
+    ST_HIP(hipMemcpyAsync(h, dstate, sizeof(State), hipMemcpyDeviceToHost, c->stream));
+    for (auto &e : c->kn_ev)
+        if (!e) ST_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    hipEvent_t ev_sw = c->kn_ev[0], ev_fix = c->kn_ev[1], ev_grp = c->kn_ev[2], ev_side = c->kn_ev[3];
+    ST_HIP(hipEventRecord(ev_sw, c->stream));
+    fix_decided(c, a, hist, fz, walk_ties, ev_grp);
+    ST_HIP(hipMemcpyAsync(h_fix, dstate, sizeof(State), hipMemcpyDeviceToHost, c->stream));
+    ST_HIP(hipEventRecord(ev_fix, c->stream));
+    ST_HIP(hipEventSynchronize(ev_sw));
+    const uint32_t npair = h->pairs;
+    const uint32_t namb = h->amb;
+    // The pair and ambiguous points' fix-ups, on the side stream beside the decided points' one
+    // when the one-device loop asks for it (c->fix_overlap) and the grouping has read the labels
+    // (hist: ev_grp was recorded, they may write theirs behind it): their ties go to a list and counters of their own (kn.ties2, kn.state2), appended to
+    // the fix-up's list afterwards (join_ties) -- the same list, in the same order, as one stream gives.
+    const bool overlap = c->fix_overlap && hist && (npair || namb) && !getenv("ST_FIX_SERIAL");
+    const Side s = overlap ? Side{side_stream(c), static_cast<State *>(ws(c, "kn.state2", sizeof(State))),
+                                  wsT<uint32_t>(c, "kn.ties2", n),
+                                  static_cast<State *>(pinned_slot(c, "kn.hside", sizeof(State)))}
+                           : Side{c->stream, dstate, a.ties, h};
+    if (overlap) {
+        ST_HIP(hipStreamWaitEvent(s.fs, ev_grp, 0));
+        ST_HIP(hipMemsetAsync(s.ds, 0, sizeof(State), s.fs));
+    }
+    if (npair) fix_pairs(c, a, s, npair);
+    mark(c, "kn.assign");
+    uint32_t ovf1 = 0;  // first lists that overflowed
+    if (namb) {
+        ovf1 = fix_ambiguous(c, a, s, namb);
+    } else if (npair) {  // the pairs' ties and counters
+        s.read_back();
+    }
+    // the decided points' fix-up (its read-back was queued behind it)
+    ST_HIP(hipEventSynchronize(ev_fix));
+    join_ties(c, a, overlap, s, npair || namb, h_fix, h, ev_side);
+    if (fz && fz->valid) {  // the fix-up's own ties are listed first; pairs and ambiguous come next
+        fz->nties_fix = h_fix->ties;
+        fz->npair = npair;
+        fz->namb = namb;
+    }
+    if (getenv("ST_DEBUG"))
+        fprintf(stderr, "[st kmeans] n=%llu k=%d pairs=%u ambiguous=%u ties=%u overflow=%u sigma=%g\n",
+                (unsigned long long)n, k, npair, namb, h->ties, h->overflow, c->kn_sigma);
+    {
+        auto &ks_ = c->kn_stats;
+        ++ks_.assigns;
+        ks_.points += n;
+        ks_.pairs += npair;
+        ks_.ambiguous += namb;
+        ks_.overflow += ovf1;
+        ks_.walked_overflow += h->overflow - ovf1;  // the second lists' overflows go to the walk
+        ks_.ties += h->ties;
+    }
+    // exact ties from k_fixrow, k_fixpair and k_exact (and candidate overflows): the KdTree walk
+    if (!walk_ties) return h->ties;
+    if (h->ties) {
+        KTimer kt(c, "kn.ties");
+        kd_resolve_ties(c, d, k, cen, a.aos, a.caos, a.ld, a.ties, h->ties, labels);
+    }
+    mark(c, "kn.exact");
+    return h->ties;
+}
 }  // namespace
 
 // The assign over the distinct centroid rows: when several centroids share a row (duplicated
@@ -2213,7 +2548,7 @@ void nd_assign(st_ctx *c, const float *const *dcols, int d, uint64_t n, int k, c
     bool grouped = try_groups && cen_groups(c, d, k, cen, &g);
     if (settle && settle()) grouped = try_groups && cen_groups(c, d, k, cen, &g);
     if (grouped) {
-        const uint32_t nties = nd_assign_core(c, dcols, d, n, (int)g.kr, g.cen_r, labels, dstate, false);
+        const uint32_t nties = nd_assign_core(c, d, n, (int)g.kr, g.cen_r, labels, dstate, false);
         const int ld = aos_ld(d);
         auto *aos = wsT<float>(c, "kn.aos", n * (size_t)ld);
         {
@@ -2231,394 +2566,83 @@ void nd_assign(st_ctx *c, const float *const *dcols, int d, uint64_t n, int k, c
         mark(c, "kn.exact");
         return;
     }
-    nd_assign_core(c, dcols, d, n, k, cen, labels, dstate, true, fz);
+    nd_assign_core(c, d, n, k, cen, labels, dstate, true, fz);
 }
-
-namespace {
-// the exact assign against the k centroids cen; exact ties go to the KdTree walk over these
-// centroids (walk_ties) or are left listed in kn.ties for the caller: returns their count
-uint32_t nd_assign_core(st_ctx *c, const float *const *dcols, int d, uint64_t n, int k, const float *cen,
-                        uint32_t *labels, km::State *dstate, bool walk_ties, NdFused *fz) {
-    ST_REQUIRE(c->kn_n == n && c->kn_d == d, ST_ERR_ARG, "kmeans assign: point set not prepared");
-    ST_REQUIRE(k <= (1 << 24), ST_ERR_UNSUPPORTED, "kmeans: K too large");
-    const int ks = kp_of(d) / 16;
-    const uint32_t ntiles = (uint32_t)((n + 31) / 32);
-    // centroid tiles, padded to whole LDS stages with rows that can never win (k_centroid_frags)
-    const uint32_t ctiles = (uint32_t)(((k + 31) / 32 + CT_STAGE - 1) / CT_STAGE * CT_STAGE);
-    auto *pfrag = wsT<uint4>(c, "kn.pfrag", (size_t)ntiles * ks * 64);
-    auto *pnorm = wsT<float>(c, "kn.pnorm", n);
-    auto *pdn = wsT<float>(c, "kn.pdn", n);
-    auto *aos = wsT<float>(c, "kn.aos", n * (size_t)aos_ld(d));
-    auto *scal = wsT<uint32_t>(c, "kn.scal", 4);
-    auto *cfrag = wsT<uint4>(c, "kn.cfrag", (size_t)ctiles * ks * 64);
-    auto *thr = wsT<float>(c, "kn.thr", n);
-    auto *amb = wsT<uint32_t>(c, "kn.amb", n);
-    auto *ties = wsT<uint32_t>(c, "kn.ties", n);
-    auto *h = static_cast<State *>(pinned(c, sizeof(State)));
-    const Bound bnd = make_bound(d, probe_denorm(c));
-    const float sigma = c->kn_sigma;
-
-    ST_HIP(hipMemsetAsync(scal + 1, 0, 8, c->stream));
-    auto *caos = wsT<float>(c, "kn.caos", (size_t)k * aos_ld(d));
-    auto *cfix = wsT<float2>(c, "kn.cfix", (size_t)ctiles * 32 * (aos_ld(d) / 2));
-    auto *cnorm = wsT<float>(c, "kn.cnorm", (size_t)ctiles * 32);
-    auto *chalf = wsT<float>(c, "kn.chalf", (size_t)ctiles * 2);
-    auto *cdn = wsT<float>(c, "kn.cdn", (size_t)ctiles * 32);
-    auto *chalf_d = wsT<float>(c, "kn.chalfd", (size_t)ctiles * 2);
-    ST_REQUIRE(ks <= CF_W, ST_ERR_INTERNAL, "kmeans: more fragments per row than centroid waves");
-    hipLaunchKernelGGL(k_centroid_frags, dim3(grid_for((uint64_t)ctiles * 32, 64, 4096)), dim3(64 * CF_W), 0, c->stream,
-                       cen, d, k, ctiles, ks, sigma, cfrag, scal + 1, caos, cfix, cnorm, cdn);
-    hipLaunchKernelGGL(k_half_max, dim3(grid_for((uint64_t)ctiles * 2, 256, 1024)), dim3(256), 0, c->stream, cnorm,
-                       cdn, ctiles * 2, chalf, chalf_d);
-    auto *ntab = wsT<float>(c, "kn.ntab", NTAB);
-    hipLaunchKernelGGL(k_norm_table, dim3(1), dim3(NTAB), 0, c->stream, cnorm, cdn, ctiles * 32, scal + 1, ntab);
-    ST_LAUNCH_CHECK();
-    auto *pair_pts = wsT<uint32_t>(c, "kn.pairpts", n);
-    auto *pair_codes = wsT<uint2>(c, "kn.paircodes", n);
-    ST_HIP(hipMemsetAsync(&dstate->amb, 0, 16, c->stream));  // amb + ties + overflow + pairs
-    const uint32_t ncodes = ctiles * 2;
-    const int ld = aos_ld(d);
-    // decided points grouped by tile-half for k_fixrow_b: the sweep counts them per code
-    const bool grouped_fix =
-        ncodes <= (uint32_t)FB_MAX_CODES && (ld == 48 || ld == 24 || ld == 12) && !getenv("ST_FIXROW_L2");
-    auto *hist = grouped_fix ? wsT<uint32_t>(c, "kn.fbhist", ncodes) : nullptr;
-    if (hist) ST_HIP(hipMemsetAsync(hist, 0, ncodes * sizeof(uint32_t), c->stream));
-    ST_KS_DISPATCH(ks, (Sweep<KS>::main(c, pfrag, ntiles, (uint32_t)n, cfrag, ctiles, pnorm, pdn, scal + 1, chalf,
-                                        chalf_d, ntab, bnd,
-                                        labels, thr, amb, dstate, pair_pts, pair_codes, hist)));
-    // the sweep's pair / ambiguous counts are final here (the fix-up only adds ties): read back
-    // behind the sweep, waited for while the fix-up runs, so that the pairs' and the ambiguous
-    // points' kernels queue up behind it with no idle gap; the fix-up's own tie count (h_fix)
-    // is read behind it and waited for only where it is needed
-    auto *h_fix = static_cast<State *>(pinned_slot(c, "kn.hfix", sizeof(State)));
-    ST_HIP(hipMemcpyAsync(h, dstate, sizeof(State), hipMemcpyDeviceToHost, c->stream));
-    for (auto &e : c->kn_ev)
-        if (!e) ST_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    hipEvent_t ev_sw = c->kn_ev[0], ev_fix = c->kn_ev[1], ev_grp = c->kn_ev[2], ev_side = c->kn_ev[3];
-    bool grouped_ev = false;
-    ST_HIP(hipEventRecord(ev_sw, c->stream));
-    if (grouped_fix) {
-        // group the decided points by tile-half, then settle them with register-resident rows
-        KTimer kt(c, "kn.fixrow");
-        auto *cursor = wsT<uint32_t>(c, "kn.fbcur", ncodes);
-        auto *ndec = wsT<uint32_t>(c, "kn.fbnd", 1);
-        // k_fixrow_lp sums DT = 45 / 24 / 9 dimensions of its LD-wide rows (the SH palettes' d):
-        // any other d in the same row width (10-12, 21-23, 46-48) takes the member-sort update
-        const bool fused = fz && fz->want && walk_ties && d == (ld == 48 ? 45 : ld == 24 ? 24 : 9);
-        // fused: the grouped points alone (a slice knows its code); otherwise (point, code) pairs
-        auto *grouped = fused ? nullptr : wsT<uint2>(c, "kn.fbpts2", n);
-        auto *grouped1 = fused ? wsT<uint32_t>(c, "kn.fbpts1", n) : nullptr;
-        auto *soff = fused ? wsT<uint32_t>(c, "kn.fasoff", (size_t)ncodes + 1) : nullptr;
-        // workgroups of the one-reservation grouping (0: k_code_scatter's 4,096-point rounds)
-        // (k_code_scatter_run reads the labels 16 bytes at a time: a caller's unaligned labels take
-        // the rounds)
-        static const int cs_env = getenv("ST_CS_WG") ? atoi(getenv("ST_CS_WG")) : 256;
-        const int cs_wg = ((uintptr_t)labels & 15u) ? 0 : cs_env;
-        const unsigned gcs = cs_wg > 0 ? grid_for(n, 256, (unsigned)cs_wg) : grid_for(n, FB_TILE, 2048);
-        if (fused) {  // slice offsets and the codes' starts in one workgroup
-            hipLaunchKernelGGL(k_fa_slices, dim3(1), dim3(FS_T), 0, c->stream, hist, ncodes, soff, cursor, ndec);
-            if (cs_wg > 0)
-                hipLaunchKernelGGL(k_code_scatter_run<uint32_t>, dim3(gcs), dim3(256), 0, c->stream, labels, (uint32_t)n,
-                                   ncodes, cursor, grouped1);
-            else
-                hipLaunchKernelGGL(k_code_scatter<uint32_t>, dim3(gcs), dim3(256), 0, c->stream, labels, (uint32_t)n,
-                                   ncodes, cursor, grouped1);
-        } else {
-            scan_u32(c, hist, cursor, ncodes, ndec);
-            if (cs_wg > 0)
-                hipLaunchKernelGGL(k_code_scatter_run<uint2>, dim3(gcs), dim3(256), 0, c->stream, labels, (uint32_t)n,
-                                   ncodes, cursor, grouped);
-            else
-                hipLaunchKernelGGL(k_code_scatter<uint2>, dim3(gcs), dim3(256), 0, c->stream, labels, (uint32_t)n,
-                                   ncodes, cursor, grouped);
-        }
-        ST_LAUNCH_CHECK();
-        // the grouping has read every label: the pair / ambiguous fix-ups may write theirs from here
-        ST_HIP(hipEventRecord(ev_grp, c->stream));
-        grouped_ev = true;
-        const dim3 g((unsigned)(((n + FB_RUN - 1) / FB_RUN * 16 + 255) / 256));
-        if (fused) {
-            // the fix-up with the decided points' sums (k_fixrow_lp), slices shared out over the workgroups
-            const uint64_t slices = ncodes + n / FA_SL + 1;
-            auto *psum = wsT<double>(c, "kn.fasum", slices * 16 * ld);
-            auto *pabs = wsT<double>(c, "kn.faabs", slices * 16 * ld);
-            auto *pemin = wsT<int>(c, "kn.faemin", slices * 16 * ld);
-            auto *pcnt = wsT<uint32_t>(c, "kn.facnt", slices * 16);
-            // the slices (their count is on the device) shared out over up to 4,096 workgroups: about
-            // one slice each at the palette shapes (1,024 stay resident; at 2,048 -- two slices per
-            // workgroup in two rounds -- the launch took 5% longer, 850 against 812 us at 10M x 45)
-            const dim3 gl((unsigned)std::min<uint64_t>(slices, 4096));
-            if (ld == 48)
-                hipLaunchKernelGGL(k_fixrow_lp<48>, gl, dim3(64 * FL_WAVES), 0, c->stream, aos, d, caos, k, grouped1, hist,
-                                   cursor, soff, ncodes, labels, ties, dstate, psum, pabs, pemin, pcnt);
-            else if (ld == 24)
-                hipLaunchKernelGGL(k_fixrow_lp<24>, gl, dim3(64 * FL_WAVES), 0, c->stream, aos, d, caos, k, grouped1, hist,
-                                   cursor, soff, ncodes, labels, ties, dstate, psum, pabs, pemin, pcnt);
-            else
-                hipLaunchKernelGGL(k_fixrow_lp<12>, gl, dim3(64 * FL_WAVES), 0, c->stream, aos, d, caos, k, grouped1, hist,
-                                   cursor, soff, ncodes, labels, ties, dstate, psum, pabs, pemin, pcnt);
-            fz->valid = true;
-            fz->ncodes = ncodes;
-        } else if (ld == 48)
-            hipLaunchKernelGGL(k_fixrow_b<48>, g, dim3(256), 0, c->stream, aos, d, caos, k, grouped, ndec, labels,
-                               ties, dstate);
-        else if (ld == 24)
-            hipLaunchKernelGGL(k_fixrow_b<24>, g, dim3(256), 0, c->stream, aos, d, caos, k, grouped, ndec, labels,
-                               ties, dstate);
-        else
-            hipLaunchKernelGGL(k_fixrow_b<12>, g, dim3(256), 0, c->stream, aos, d, caos, k, grouped, ndec, labels,
-                               ties, dstate);
-        ST_LAUNCH_CHECK();
-    } else {
-        KTimer kt(c, "kn.fixrow");
-        hipLaunchKernelGGL(k_fixrow, dim3((unsigned)((n * 16 + 255) / 256)), dim3(256), 0, c->stream, aos, d, cfix,
-                           caos, k, (uint32_t)n, labels, ties, dstate);
-        ST_LAUNCH_CHECK();
-    }
-    ST_HIP(hipMemcpyAsync(h_fix, dstate, sizeof(State), hipMemcpyDeviceToHost, c->stream));
-    ST_HIP(hipEventRecord(ev_fix, c->stream));
-    ST_HIP(hipEventSynchronize(ev_sw));
-    const uint32_t npair = h->pairs;
-    const uint32_t namb = h->amb;
-    // The pair and ambiguous points' fix-ups, on the side stream beside the decided points' one
-    // when the one-device loop asks for it (c->fix_overlap) and the grouping has read the labels
-    // (ev_grp): their ties go to a list and counters of their own (kn.ties2, kn.state2), appended to
-    // the fix-up's list afterwards -- the same list, in the same order, as one stream gives.
-    const bool overlap = c->fix_overlap && grouped_ev && (npair || namb) && !getenv("ST_FIX_SERIAL");
-    const hipStream_t fs = overlap ? side_stream(c) : c->stream;
-    State *ds = overlap ? static_cast<State *>(ws(c, "kn.state2", sizeof(State))) : dstate;
-    uint32_t *tl = overlap ? wsT<uint32_t>(c, "kn.ties2", n) : ties;
-    auto *hs = overlap ? static_cast<State *>(pinned_slot(c, "kn.hside", sizeof(State))) : h;
-    if (overlap) {
-        ST_HIP(hipStreamWaitEvent(fs, ev_grp, 0));
-        ST_HIP(hipMemsetAsync(ds, 0, sizeof(State), fs));
-    }
-    if (npair) {
-        KTimer kt(c, "kn.fixpair", fs);
-        const dim3 g((npair * 32 + 255) / 256);
-        if (ld == 48)
-            hipLaunchKernelGGL(k_fixpair_b<48>, g, dim3(256), 0, fs, aos, d, cfix, caos, k, pair_pts,
-                               pair_codes, npair, labels, tl, ds);
-        else if (ld == 24)
-            hipLaunchKernelGGL(k_fixpair_b<24>, g, dim3(256), 0, fs, aos, d, cfix, caos, k, pair_pts,
-                               pair_codes, npair, labels, tl, ds);
-        else if (ld == 12)
-            hipLaunchKernelGGL(k_fixpair_b<12>, g, dim3(256), 0, fs, aos, d, cfix, caos, k, pair_pts,
-                               pair_codes, npair, labels, tl, ds);
-        else
-            hipLaunchKernelGGL(k_fixpair, g, dim3(256), 0, fs, aos, d, cfix, caos, k, pair_pts, pair_codes,
-                               npair, labels, tl, ds);
-        ST_LAUNCH_CHECK();
-    }
-    mark(c, "kn.assign");
-    uint32_t ovf1 = 0;  // first lists that overflowed (collected again with CAND_CAP2)
-    if (namb) {
-        const uint32_t atiles = (namb + 31) / 32;
-        auto *afrag = wsT<uint4>(c, "kn.afrag", (size_t)atiles * ks * 64);
-        auto *thr_slot = wsT<float>(c, "kn.thrslot", (size_t)atiles * 32);
-        auto *cand_cnt = wsT<uint32_t>(c, "kn.ccnt", (size_t)atiles * 32);
-        auto *cand = wsT<uint32_t>(c, "kn.cand", (size_t)namb * CAND_CAP);
-        hipLaunchKernelGGL(k_gather_amb, dim3(grid_for((uint64_t)atiles * 32, 256, 4096)), dim3(256), 0, fs,
-                           pfrag, amb, thr, namb, ks, afrag, thr_slot, cand_cnt);
-        ST_LAUNCH_CHECK();
-        auto *ovf = wsT<uint32_t>(c, "kn.ovf", namb);
-        ST_KS_DISPATCH(ks, (Sweep<KS>::collect(c, afrag, atiles, namb, cfrag, ctiles, bnd, thr_slot, cand_cnt, cand,
-                                               (uint32_t)CAND_CAP, fs)));
-        {
-            KTimer kt(c, "kn.exact", fs);
-            hipLaunchKernelGGL(k_exact, dim3((namb + 3) / 4), dim3(256), 0, fs, aos, d, caos, k, amb, namb,
-                               cand_cnt, cand, (uint32_t)CAND_CAP, labels, tl, ovf, ds);
-            ST_LAUNCH_CHECK();
-        }
-        ST_HIP(hipMemcpyAsync(hs, ds, sizeof(State), hipMemcpyDeviceToHost, fs));
-        ST_HIP(hipStreamSynchronize(fs));
-        ovf1 = hs->overflow;
-        if (hs->overflow) {
-            // points whose window holds more than CAND_CAP rows (wide windows: outlying points of
-            // heavy-tailed data): collected again with lists of CAND_CAP2, in batches; only those
-            // that overflow these too take the KdTree walk
-            const uint32_t nov = hs->overflow, batch = std::min(nov, (uint32_t)OVF_BATCH);
-            const uint32_t btiles = (batch + 31) / 32;
-            auto *afrag2 = wsT<uint4>(c, "kn.afrag2", (size_t)btiles * ks * 64);
-            auto *thr2 = wsT<float>(c, "kn.thrslot2", (size_t)btiles * 32);
-            auto *cnt2 = wsT<uint32_t>(c, "kn.ccnt2", (size_t)btiles * 32);
-            auto *cand2 = wsT<uint32_t>(c, "kn.cand2", (size_t)batch * CAND_CAP2);
-            for (uint32_t b0 = 0; b0 < nov; b0 += batch) {
-                const uint32_t m = std::min(batch, nov - b0), mt = (m + 31) / 32;
-                hipLaunchKernelGGL(k_gather_amb, dim3(grid_for((uint64_t)mt * 32, 256, 4096)), dim3(256), 0, fs,
-                                   pfrag, ovf + b0, thr, m, ks, afrag2, thr2, cnt2);
-                ST_LAUNCH_CHECK();
-                ST_KS_DISPATCH(ks, (Sweep<KS>::collect(c, afrag2, mt, m, cfrag, ctiles, bnd, thr2, cnt2, cand2,
-                                                       (uint32_t)CAND_CAP2, fs)));
-                KTimer kt(c, "kn.exact", fs);
-                hipLaunchKernelGGL(k_exact, dim3((m + 3) / 4), dim3(256), 0, fs, aos, d, caos, k, ovf + b0, m,
-                                   cnt2, cand2, (uint32_t)CAND_CAP2, labels, tl, (uint32_t *)nullptr, ds);
-                ST_LAUNCH_CHECK();
-            }
-            ST_HIP(hipMemcpyAsync(hs, ds, sizeof(State), hipMemcpyDeviceToHost, fs));
-            ST_HIP(hipStreamSynchronize(fs));
-        }
-        if (getenv("ST_DEBUG")) {  // candidate-count histogram of the ambiguous points
-            std::vector<uint32_t> cc(namb);
-            ST_HIP(hipMemcpy(cc.data(), cand_cnt, namb * 4, hipMemcpyDeviceToHost));
-            uint64_t hist[6] = {0, 0, 0, 0, 0, 0};
-            for (uint32_t v : cc) ++hist[v < 5 ? v : 5];
-            fprintf(stderr, "[st kmeans] candidates per ambiguous point: 0:%llu 1:%llu 2:%llu 3:%llu 4:%llu 5+:%llu\n",
-                    (unsigned long long)hist[0], (unsigned long long)hist[1], (unsigned long long)hist[2],
-                    (unsigned long long)hist[3], (unsigned long long)hist[4], (unsigned long long)hist[5]);
-        }
-    } else if (npair) {  // the pairs' ties and counters
-        ST_HIP(hipMemcpyAsync(hs, ds, sizeof(State), hipMemcpyDeviceToHost, fs));
-        ST_HIP(hipStreamSynchronize(fs));
-    }
-    // the decided points' fix-up (its read-back was queued behind it)
-    ST_HIP(hipEventSynchronize(ev_fix));
-    const uint32_t nties_fix = h_fix->ties;
-    if (overlap) {
-        // join: the side stream's ties follow the fix-up's in one list (kn.ties), as one stream
-        // would have listed them; its overflow count is the assign's
-        ST_HIP(hipEventRecord(ev_side, fs));
-        ST_HIP(hipStreamWaitEvent(c->stream, ev_side, 0));
-        if (hs->ties)
-            ST_HIP(hipMemcpyAsync(ties + nties_fix, tl, (size_t)hs->ties * sizeof(uint32_t), hipMemcpyDeviceToDevice,
-                                  c->stream));
-        *h = *h_fix;
-        h->ties = nties_fix + hs->ties;
-        h->overflow = hs->overflow;
-    } else if (!npair && !namb) {
-        *h = *h_fix;
-    }
-    if (fz && fz->valid) {  // the fix-up's own ties are listed first; pairs and ambiguous come next
-        fz->nties_fix = nties_fix;
-        fz->npair = npair;
-        fz->namb = namb;
-    }
-    if (getenv("ST_DEBUG"))
-        fprintf(stderr, "[st kmeans] n=%llu k=%d pairs=%u ambiguous=%u ties=%u overflow=%u sigma=%g\n",
-                (unsigned long long)n, k, npair, namb, h->ties, h->overflow, sigma);
-    {
-        auto &ks_ = c->kn_stats;
-        ++ks_.assigns;
-        ks_.points += n;
-        ks_.pairs += npair;
-        ks_.ambiguous += namb;
-        ks_.overflow += ovf1;
-        ks_.walked_overflow += h->overflow - ovf1;  // the second lists' overflows go to the walk
-        ks_.ties += h->ties;
-    }
-    // exact ties from k_fixrow, k_fixpair and k_exact (and candidate overflows): the KdTree walk
-    if (!walk_ties) return h->ties;
-    if (h->ties) {
-        KTimer kt(c, "kn.ties");
-        kd_resolve_ties(c, d, k, cen, aos, caos, ld, ties, h->ties, labels);
-    }
-    mark(c, "kn.exact");
-    return h->ties;
-}
-}  // namespace
 
 namespace {
 // the points the fused fix-up did not sum (pairs, ambiguous, its own exact ties), sorted by final
-// label: kn.ovals in label order, kn.ostart their cluster ranges; returns their count
-uint32_t others_sort(st_ctx *c, uint64_t n, int k, const NdFused &fz, const uint32_t *labels) {
-    const uint32_t m = fz.npair + fz.namb + fz.nties_fix;
-    auto *okeys = wsT<uint32_t>(c, "kn.okeys", (size_t)m + 1);
-    auto *ovals = wsT<uint32_t>(c, "kn.ovals", (size_t)m + 1);
-    auto *ostart = wsT<uint32_t>(c, "kn.ostart", (size_t)k + 1);
-    if (m) {
-        hipLaunchKernelGGL(k_others_keys, dim3(grid_for(m, 256, 4096)), dim3(256), 0, c->stream,
+// label, with the list of clusters that hold more than `split` of them (others_split())
+struct OthersWs {  // OthersWs{c, k, m}
+    st_ctx *c;
+    int k;
+    uint32_t m;  // the others' count
+    uint32_t split = others_split();
+    uint32_t *okeys = wsT<uint32_t>(c, "kn.okeys", (size_t)m + 1);    // sort keys (labels)
+    uint32_t *ovals = wsT<uint32_t>(c, "kn.ovals", (size_t)m + 1);    // the points in label order
+    uint32_t *ostart = wsT<uint32_t>(c, "kn.ostart", (size_t)k + 1);  // their cluster ranges
+    // the heavy clusters, listed by k_nd_combine / k_nd_partials
+    uint32_t *heavy = wsT<uint32_t>(c, "kn.heavy", (size_t)m / split + 2);
+};
+
+// o.ovals and o.ostart from the assign's lists and the final labels
+void others_sort(st_ctx *c, uint64_t n, int k, const NdFused &fz, const uint32_t *labels, const OthersWs &o) {
+    if (o.m) {
+        hipLaunchKernelGGL(k_others_keys, dim3(grid_for(o.m, 256, 4096)), dim3(256), 0, c->stream,
                            wsT<uint32_t>(c, "kn.pairpts", n), fz.npair, wsT<uint32_t>(c, "kn.amb", n), fz.namb,
-                           wsT<uint32_t>(c, "kn.ties", n), fz.nties_fix, labels, okeys, ovals);
+                           wsT<uint32_t>(c, "kn.ties", n), fz.nties_fix, labels, o.okeys, o.ovals);
         ST_LAUNCH_CHECK();
         int bits = 1;
         while ((1ull << bits) < (uint64_t)k) ++bits;
-        radix_sort_u32(c, okeys, ovals, m, 0, bits, "kn.osort");
+        radix_sort_u32(c, o.okeys, o.ovals, o.m, 0, bits, "kn.osort");
     }
-    bounds_from_sorted(c, okeys, m, k, ostart);
-    return m;
+    bounds_from_sorted(c, o.okeys, o.m, k, o.ostart);
 }
-}  // namespace
 
-namespace {
-// the update after a fused fix-up: the other points' sums by label, the certified centroids,
-// the sequential sums of the clusters the certificate fails.  Returns false when a flagged
-// cluster has more members than k_nd_seq takes: those are summed over the member sort.
-// the clusters k_nd_combine / k_nd_partials listed as heavy (heavy / nheavy on the device): their
+// the clusters k_nd_combine / k_nd_partials listed as heavy (o.heavy / nheavy on the device): their
 // others' chunk records, then one wave each (no host sync)
-template <int LD, bool SHARD>
-void heavy_pass_t(st_ctx *c, int d, uint64_t n, int k, uint32_t m, const float *aos, const uint32_t *soff,
-                  const double *psum, const double *pabs, const int *pemin, const uint32_t *pcnt,
-                  const uint32_t *ostart, const uint32_t *ovals, const uint32_t *heavy, const uint32_t *nheavy,
-                  float *cen, uint32_t *counts, uint32_t *flagged, uint32_t *nflagged, double *sums, double *sabs,
-                  int32_t *emin) {
-    (void)n;
-    const uint32_t split = others_split(), chunk = others_chunk();
-    const uint64_t chunks = m / chunk + m / split + 2;  // bound: every heavy cluster holds > split others
+template <bool SHARD>
+void heavy_pass(st_ctx *c, int ld, int d, int k, const float *aos, const FusedWs &f, const OthersWs &o,
+                uint32_t *nheavy, float *cen, uint32_t *counts, uint32_t *flagged, uint32_t *nflagged, double *sums,
+                double *sabs, int32_t *emin) {
+    if (o.m <= o.split) return;  // no cluster can hold more others than there are
+    const uint32_t chunk = others_chunk();
+    const uint64_t chunks = o.m / chunk + o.m / o.split + 2;  // bound: every heavy cluster holds > split others
     auto *rsum = wsT<double>(c, "kn.hrsum", chunks * 64);
     auto *rabs = wsT<double>(c, "kn.hrabs", chunks * 64);
     auto *remin = wsT<int>(c, "kn.hremin", chunks * 64);
-    hipLaunchKernelGGL((k_heavy<LD, SHARD>), dim3(grid_for(chunks, 1, 2048)), dim3(256), 0, c->stream, aos, d, k, soff,
-                       psum, pabs, pemin, pcnt, ostart, ovals, heavy, nheavy, const_cast<uint32_t *>(nheavy) + 1, chunk, rsum, rabs, remin,
-                       cen, counts, flagged, nflagged, sums, sabs, emin);
+    ST_LD_DISPATCH(ld, hipLaunchKernelGGL((k_heavy<LD, SHARD>), dim3(grid_for(chunks, 1, 2048)), dim3(256), 0,
+                                          c->stream, aos, d, k, f.soff, f.psum, f.pabs, f.pemin, f.pcnt, o.ostart,
+                                          o.ovals, o.heavy, nheavy, nheavy + 1, chunk, rsum, rabs, remin, cen, counts,
+                                          flagged, nflagged, sums, sabs, emin));
     ST_LAUNCH_CHECK();
 }
 
-template <bool SHARD>
-void heavy_pass(st_ctx *c, int ld, int d, uint64_t n, int k, uint32_t m, const float *aos, const uint32_t *soff,
-                const double *psum, const double *pabs, const int *pemin, const uint32_t *pcnt, const uint32_t *ostart,
-                const uint32_t *ovals, const uint32_t *heavy, const uint32_t *nheavy, float *cen, uint32_t *counts,
-                uint32_t *flagged, uint32_t *nflagged, double *sums, double *sabs, int32_t *emin) {
-    if (m <= others_split()) return;  // no cluster can hold more others than there are
-    if (ld == 48)
-        heavy_pass_t<48, SHARD>(c, d, n, k, m, aos, soff, psum, pabs, pemin, pcnt, ostart, ovals, heavy, nheavy, cen,
-                                counts, flagged, nflagged, sums, sabs, emin);
-    else if (ld == 24)
-        heavy_pass_t<24, SHARD>(c, d, n, k, m, aos, soff, psum, pabs, pemin, pcnt, ostart, ovals, heavy, nheavy, cen,
-                                counts, flagged, nflagged, sums, sabs, emin);
-    else
-        heavy_pass_t<12, SHARD>(c, d, n, k, m, aos, soff, psum, pabs, pemin, pcnt, ostart, ovals, heavy, nheavy, cen,
-                                counts, flagged, nflagged, sums, sabs, emin);
-}
-
-bool nd_fused_update(st_ctx *c, int d, uint64_t n, int k, const NdFused &fz, const uint32_t *labels, float *cen,
-                     uint32_t *counts, State *dstate) {
+// the update after a fused fix-up: the other points' sums by label, the certified centroids,
+// the sequential sums of the clusters the certificate fails.  A flagged cluster with more
+// members than k_nd_seq takes is listed (kn.big) and summed over the member sort by nd_big_sums.
+void nd_fused_update(st_ctx *c, int d, uint64_t n, int k, const NdFused &fz, const uint32_t *labels, float *cen,
+                     uint32_t *counts) {
     KTimer kt(c, "kn.sumnd");
     const int ld = aos_ld(d);
     auto *aos = wsT<float>(c, "kn.aos", n * (size_t)ld);
-    const uint64_t slices = fz.ncodes + n / FA_SL + 1;
-    auto *soff = wsT<uint32_t>(c, "kn.fasoff", (size_t)fz.ncodes + 1);
-    auto *psum = wsT<double>(c, "kn.fasum", slices * 16 * ld);
-    auto *pabs = wsT<double>(c, "kn.faabs", slices * 16 * ld);
-    auto *pemin = wsT<int>(c, "kn.faemin", slices * 16 * ld);
-    auto *pcnt = wsT<uint32_t>(c, "kn.facnt", slices * 16);
-    const uint32_t m = others_sort(c, n, k, fz, labels);
-    auto *ovals = wsT<uint32_t>(c, "kn.ovals", (size_t)m + 1);
-    auto *ostart = wsT<uint32_t>(c, "kn.ostart", (size_t)k + 1);
+    const FusedWs f{c, n, ld, fz.ncodes};
+    const OthersWs o{c, k, fz.npair + fz.namb + fz.nties_fix};
+    others_sort(c, n, k, fz, labels, o);
     auto *flagged = wsT<uint32_t>(c, "kn.flagged", (size_t)k);
     // [0] flagged clusters, [1] collect overflow, [2] heavy clusters, [3] k_heavy's finished workgroups
     auto *nflag = wsT<uint32_t>(c, "kn.nflag", 4);
-    const uint32_t split = others_split();
-    auto *heavy = wsT<uint32_t>(c, "kn.heavy", (size_t)m / split + 2);
     ST_HIP(hipMemsetAsync(nflag, 0, 16, c->stream));
-    const dim3 g((k + 3) / 4);
-    if (ld == 48)
-        hipLaunchKernelGGL(k_nd_combine<48>, g, dim3(256), 0, c->stream, aos, d, k, soff, psum, pabs, pemin, pcnt,
-                           ostart, ovals, cen, counts, flagged, nflag, heavy, nflag + 2, split);
-    else if (ld == 24)
-        hipLaunchKernelGGL(k_nd_combine<24>, g, dim3(256), 0, c->stream, aos, d, k, soff, psum, pabs, pemin, pcnt,
-                           ostart, ovals, cen, counts, flagged, nflag, heavy, nflag + 2, split);
-    else
-        hipLaunchKernelGGL(k_nd_combine<12>, g, dim3(256), 0, c->stream, aos, d, k, soff, psum, pabs, pemin, pcnt,
-                           ostart, ovals, cen, counts, flagged, nflag, heavy, nflag + 2, split);
+    ST_LD_DISPATCH(ld, hipLaunchKernelGGL(k_nd_combine<LD>, dim3((k + 3) / 4), dim3(256), 0, c->stream, aos, d, k,
+                                          f.soff, f.psum, f.pabs, f.pemin, f.pcnt, o.ostart, o.ovals, cen, counts,
+                                          flagged, nflag, o.heavy, nflag + 2, o.split));
     ST_LAUNCH_CHECK();
-    heavy_pass<false>(c, ld, d, n, k, m, aos, soff, psum, pabs, pemin, pcnt, ostart, ovals, heavy, nflag + 2, cen,
-                      counts, flagged, nflag, nullptr, nullptr, nullptr);
+    heavy_pass<false>(c, ld, d, k, aos, f, o, nflag + 2, cen, counts, flagged, nflag, nullptr, nullptr, nullptr);
     // the clusters the certificate fails: their members in point order, the sequential sums
     // (grid-stride over the flagged list; none: every workgroup returns at once)
     auto *big = wsT<uint32_t>(c, "kn.big", (size_t)k);
     hipLaunchKernelGGL(k_nd_seq, dim3(256), dim3(256), 0, c->stream, aos, d, k, flagged, nflag,
                        wsT<uint32_t>(c, "kn.fbpts1", n), wsT<uint32_t>(c, "kn.fbhist", fz.ncodes),
-                       wsT<uint32_t>(c, "kn.fbcur", fz.ncodes), labels, ostart, ovals, cen, big, nflag + 1);
+                       wsT<uint32_t>(c, "kn.fbcur", fz.ncodes), labels, o.ostart, o.ovals, cen, big, nflag + 1);
     ST_LAUNCH_CHECK();
     // the count of uncertified clusters too large for k_nd_seq is read at the next host sync
     // (nd_big_sums, before anything reads these centroids): no sync of its own
@@ -2626,10 +2650,9 @@ bool nd_fused_update(st_ctx *c, int d, uint64_t n, int k, const NdFused &fz, con
     ST_HIP(hipMemcpyAsync(h, nflag, 8, hipMemcpyDeviceToHost, c->stream));
     if (getenv("ST_DEBUG")) {
         ST_HIP(hipStreamSynchronize(c->stream));
-        fprintf(stderr, "[st kmeans] fused update: others=%u uncertified clusters=%u over %u members=%u\n", m, h[0],
+        fprintf(stderr, "[st kmeans] fused update: others=%u uncertified clusters=%u over %u members=%u\n", o.m, h[0],
                 NS_CAP, h[1]);
     }
-    return true;
 }
 
 // the fused update's pending count (kn.hflag, copied behind its kernels): the clusters k_nd_seq
@@ -2644,17 +2667,8 @@ bool nd_big_sums(st_ctx *c, int d, uint64_t n, int k, const uint32_t *labels, fl
     auto *members = wsT<uint32_t>(c, "kn.members", n);
     auto *start = wsT<uint32_t>(c, "kn.start", (size_t)k + 1);
     member_sort(c, labels, n, k, sorted_labels, members, start);
-    // the listed clusters: one wave each up to sumnd_big() members, the huge ones (a cluster of
-    // the table's all-zero rows) sliced over the chip (big_sums)
-    const uint32_t big = sumnd_big();
-    const uint32_t cap = (uint32_t)(n / ((uint64_t)big + 1) + 1);
-    auto *list = wsT<uint32_t>(c, "kn.blist", cap);
-    auto *nlist = wsT<uint32_t>(c, "kn.bn", 1);
-    ST_HIP(hipMemsetAsync(nlist, 0, 4, c->stream));
-    hipLaunchKernelGGL(k_sumnd<float>, dim3((nbig + 3) / 4), dim3(256), 0, c->stream, aos, d, members, start, k, cen,
-                       big, cap, list, nlist, wsT<uint32_t>(c, "kn.big", (size_t)k), wsT<uint32_t>(c, "kn.nflag", 2) + 1);
-    ST_LAUNCH_CHECK();
-    if (n > big) big_sums(c, aos, d, n, k, members, start, cen, cap, list, nlist);
+    launch_sums<float>(c, aos, d, n, k, members, start, cen, wsT<uint32_t>(c, "kn.big", (size_t)k),
+                       wsT<uint32_t>(c, "kn.nflag", 2) + 1, nbig);
     return true;
 }
 }  // namespace
@@ -2664,38 +2678,20 @@ void nd_fused_partials(st_ctx *c, int d, uint64_t n, int k, const NdFused &fz, c
     KTimer kt(c, "kn.partials");
     const int ld = aos_ld(d);
     auto *aos = wsT<float>(c, "kn.aos", n * (size_t)ld);
-    const uint64_t slices = fz.ncodes + n / FA_SL + 1;
-    auto *soff = wsT<uint32_t>(c, "kn.fasoff", (size_t)fz.ncodes + 1);
-    auto *psum = wsT<double>(c, "kn.fasum", slices * 16 * ld);
-    auto *pabs = wsT<double>(c, "kn.faabs", slices * 16 * ld);
-    auto *pemin = wsT<int>(c, "kn.faemin", slices * 16 * ld);
-    auto *pcnt = wsT<uint32_t>(c, "kn.facnt", slices * 16);
-    const uint32_t m = others_sort(c, n, k, fz, labels);
-    auto *ovals = wsT<uint32_t>(c, "kn.ovals", (size_t)m + 1);
-    auto *ostart = wsT<uint32_t>(c, "kn.ostart", (size_t)k + 1);
+    const FusedWs f{c, n, ld, fz.ncodes};
+    const OthersWs o{c, k, fz.npair + fz.namb + fz.nties_fix};
+    others_sort(c, n, k, fz, labels, o);
     auto *nheavy = wsT<uint32_t>(c, "kn.pnheavy", 2);  // [0] heavy clusters, [1] k_heavy's finished workgroups
-    const uint32_t split = others_split();
-    auto *heavy = wsT<uint32_t>(c, "kn.heavy", (size_t)m / split + 2);
     ST_HIP(hipMemsetAsync(nheavy, 0, 8, c->stream));
-    const dim3 g((k + 3) / 4);
-    if (ld == 48)
-        hipLaunchKernelGGL(k_nd_partials<48>, g, dim3(256), 0, c->stream, aos, d, k, soff, psum, pabs, pemin, pcnt,
-                           ostart, ovals, sums, sabs, emin, counts, heavy, nheavy, split);
-    else if (ld == 24)
-        hipLaunchKernelGGL(k_nd_partials<24>, g, dim3(256), 0, c->stream, aos, d, k, soff, psum, pabs, pemin, pcnt,
-                           ostart, ovals, sums, sabs, emin, counts, heavy, nheavy, split);
-    else
-        hipLaunchKernelGGL(k_nd_partials<12>, g, dim3(256), 0, c->stream, aos, d, k, soff, psum, pabs, pemin, pcnt,
-                           ostart, ovals, sums, sabs, emin, counts, heavy, nheavy, split);
+    ST_LD_DISPATCH(ld, hipLaunchKernelGGL(k_nd_partials<LD>, dim3((k + 3) / 4), dim3(256), 0, c->stream, aos, d, k,
+                                          f.soff, f.psum, f.pabs, f.pemin, f.pcnt, o.ostart, o.ovals, sums, sabs, emin,
+                                          counts, o.heavy, nheavy, o.split));
     ST_LAUNCH_CHECK();
-    heavy_pass<true>(c, ld, d, n, k, m, aos, soff, psum, pabs, pemin, pcnt, ostart, ovals, heavy, nheavy, nullptr,
-                     counts, nullptr, nullptr, sums, sabs, emin);
+    heavy_pass<true>(c, ld, d, k, aos, f, o, nheavy, nullptr, counts, nullptr, nullptr, sums, sabs, emin);
 }
 
-void kmeansnd_loop(st_ctx *c, const float *const *cols, const float *const *dcols, int d, uint64_t n, int k,
-                   int iters, const double *ddraws, uint64_t ndraws, km::State *dstate, float *cen, uint32_t *labels,
-                   const double *const *sum64) {
-    (void)cols;
+void kmeansnd_loop(st_ctx *c, const float *const *dcols, int d, uint64_t n, int k, int iters, const double *ddraws,
+                   uint64_t ndraws, km::State *dstate, float *cen, uint32_t *labels, const double *const *sum64) {
     // one device: the assign's pair / ambiguous fix-ups overlap the decided points' (nd_assign_core)
     struct Overlap {
         st_ctx *c;
@@ -2735,7 +2731,8 @@ void kmeansnd_loop(st_ctx *c, const float *const *cols, const float *const *dcol
         fz.want = !aos64 && !getenv("ST_ND_SORT");
         nd_assign(c, dcols, d, n, k, cen, labels, dstate, &fz, pending ? settle : std::function<bool()>());
         // update
-        if (fz.valid && nd_fused_update(c, d, n, k, fz, labels, cen, counts, dstate)) {
+        if (fz.valid) {
+            nd_fused_update(c, d, n, k, fz, labels, cen, counts);
             reseed_empty_counts(c, dcols, d, n, k, counts, ddraws, ndraws, dstate, cen);
             pending = true;
         } else {

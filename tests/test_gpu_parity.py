@@ -183,6 +183,56 @@ def test_kmeans_vs_oracle(ctx, n, d, k, iters, dist):
         assert st['pairs'] + st['ambiguous'] <= st['points']
 
 
+def kmeans_hooked_vs_oracle(ctx, monkeypatch, hooks, n, d, k, iters, dist='gauss'):
+    """test_kmeans_vs_oracle's comparison (labels, centroids, draws used) with environment hooks
+    set around the call; returns the assigns' statistics"""
+    for name in hooks:
+        monkeypatch.setenv(name, hooks[name])
+    rng = np.random.default_rng(n + d)
+    cols = ([rng.normal(0, 0.1, n).astype(np.float32) for _ in range(d)] if dist == 'gauss'
+            else heavy_tailed(rng, n, d))
+    draws = oracle.mulberry32(n + k, 4 * k * (iters + 1) + 64)
+    cent, labels, used = ctx.kmeans(cols, k, iters, draws)
+    rc, ocent, olabels, oused = oracle.kmeans(cols, k, iters, draws)
+    assert rc == 0 and used == oused
+    same_bits(labels, olabels)
+    same_bits(cent, ocent)
+    return ctx.kmeans_stats()
+
+
+@pytest.mark.parametrize('n,d,k,iters', [(20_000, 45, 1024, 2), (30_000, 24, 2048, 2)])
+def test_kmeans_fixrow_l2_vs_oracle(ctx, monkeypatch, n, d, k, iters):
+    """ST_FIXROW_L2: the decided points stay ungrouped and k_fixrow settles them at a palette row
+    width (48, 24) -- the path K > 131,072 takes there -- followed by the member-sort update"""
+    kmeans_hooked_vs_oracle(ctx, monkeypatch, {'ST_FIXROW_L2': '1'}, n, d, k, iters)
+
+
+def test_kmeans_fix_serial_vs_oracle(ctx, monkeypatch):
+    """ST_FIX_SERIAL: the pair and ambiguous points' fix-ups queue behind the decided points' one on
+    the one stream (the join's serial case) in the one-device loop, which otherwise overlaps them"""
+    st = kmeans_hooked_vs_oracle(ctx, monkeypatch, {'ST_FIX_SERIAL': '1'}, 20_000, 45, 1024, 3, 't3')
+    assert st['pairs'] > 0 and st['ambiguous'] > 0  # the side fix-ups ran
+
+
+@pytest.mark.parametrize('sort', [False, True])
+def test_kmeans_code_scatter_rounds_vs_oracle(ctx, monkeypatch, sort):
+    """ST_CS_WG=0: the decided points are grouped by k_code_scatter's 4,096-point rounds, not the
+    one-reservation k_code_scatter_run: points alone for the fused fix-up, (point, code) pairs
+    for k_fixrow_b under ST_ND_SORT"""
+    hooks = {'ST_CS_WG': '0'}
+    if sort:
+        hooks['ST_ND_SORT'] = '1'
+    kmeans_hooked_vs_oracle(ctx, monkeypatch, hooks, 20_000, 45, 1024, 2)
+
+
+@pytest.mark.parametrize('d', [16, 30])
+def test_kmeans_generic_pairs_vs_oracle(ctx, monkeypatch, d):
+    """row widths outside 12 / 24 / 48 (d = 16: 16, d = 30: 32) with pair points: the generic
+    k_fixpair beside k_fixrow.  k = 1,024 gives pair points at both d."""
+    st = kmeans_hooked_vs_oracle(ctx, monkeypatch, {}, 20_000, d, 1024, 2)
+    assert st['pairs'] > 0
+
+
 @pytest.mark.parametrize('n,k,tiny_frac', [(20_000, 257, 0.0), (20_000, 257, 0.02), (20_000, 4096, 0.02),
                                            (20_000, 4097, 0.02), (600_000, 300, 0.02)])
 def test_kmeans_1d_general_vs_oracle(ctx, n, k, tiny_frac, monkeypatch, capfd):
