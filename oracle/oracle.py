@@ -271,8 +271,9 @@ def _band_coeffs(names):
 def process(cols, actions):
     """processDataTable (process.ts:64-145) over a list of (name, array): actions are dicts with
     'kind' translate / rotate (Euler degrees) / scale / filterNaN / filterByValue (columnName,
-    comparator, value) / filterBands (value) / param.  transform() runs in the C restatement on
-    the float32 columns; the filters are numpy predicates + the permuteRows gather; filterBands
+    comparator, value) / filterBands (value) / param.  transform() runs in the C restatement when
+    every column is float32 and in oracle_typed.transform (JS numbers in, TypedArray stores out) when any
+    column has another type; the filters are numpy predicates + the permuteRows gather; filterBands
     renames / drops f_rest columns against the ORIGINAL table's band (process.ts:111)."""
     cols = [(k, np.array(a, copy=True)) for k, a in cols]
     in_coeffs = _band_coeffs([k for k, _ in cols])
@@ -282,9 +283,12 @@ def process(cols, actions):
             v = act['value']
             p = (transform_params(t=v) if kind == 'translate' else
                  transform_params(euler=v) if kind == 'rotate' else transform_params(s=float(v)))
-            f32 = {k: a for k, a in cols if a.dtype == np.float32}
-            if f32:
-                transform(f32, p, _band_coeffs(list(f32)))
+            if all(a.dtype == np.float32 for _, a in cols):
+                d = dict(cols)
+                transform(d, p, _band_coeffs(list(d)))
+            else:  # getRow / setRow on any column type: the numpy restatement (oracle/oracle_typed.py)
+                import oracle_typed
+                oracle_typed.transform(dict(cols), p)
         elif kind == 'filterNaN':
             cols, _ = filter_nan(cols)
         elif kind == 'filterByValue':

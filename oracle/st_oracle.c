@@ -148,7 +148,9 @@ double st_o_log(double x)
     k = 0;
     if (hx < 0x00100000) {
         if (((hx & 0x7fffffff) | lx) == 0) return -two54 / vzero;
-        if (hx < 0) return (x - x) / vzero;
+        /* V8's ieee754::log: std::numeric_limits<double>::signaling_NaN() for every argument with
+         * the sign bit set other than -0 (0x7ff4000000000000; 0x7fe00000 in a Float32Array) */
+        if (hx < 0) return from_words(0x7ff40000u, 0);
         k -= 54;
         x *= two54;
         hx = (int32_t)hi_word(x);
@@ -193,6 +195,11 @@ double st_o_log(double x)
 void st_o_log_n(uint64_t n, const double *x, double *out)
 {
     for (uint64_t i = 0; i < n; ++i) out[i] = st_o_log(x[i]);
+}
+
+void st_o_exp_n(uint64_t n, const double *x, double *out)
+{
+    for (uint64_t i = 0; i < n; ++i) out[i] = st_o_exp(x[i]);
 }
 
 static inline double sigmoid(double v) { return 1 / (1 + st_o_exp(-v)); } /* utils/math.ts:1 */

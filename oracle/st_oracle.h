@@ -23,6 +23,8 @@ double st_o_exp(double x);
 double st_o_log(double x);
 /* st_o_log over an array (the readers' restatement, oracle/readers.py) */
 void st_o_log_n(uint64_t n, const double *x, double *out);
+/* st_o_exp over an array (the typed-column restatement, oracle/oracle_typed.py) */
+void st_o_exp_n(uint64_t n, const double *x, double *out);
 
 /* PlayCanvas 2.11.8 math restated (process.ts:75-79, transform.ts:13-14). */
 void st_o_quat_from_euler(double ex, double ey, double ez, double q_xyzw[4]);

@@ -53,6 +53,16 @@ __host__ __device__ inline float x86_nanf(float r, bool nan_in) {
     return (r != r && !nan_in) ? __builtin_bit_cast(float, 0xffc00000u) : r;
 }
 
+// a Float32Array store of v.  A NaN keeps its sign and the top of its payload with the quiet bit
+// set, as cvtsd2ss does: the signalling NaN of js::log becomes 0x7fe00000, the default NaN
+// 0xffc00000.  Written out so that the bits do not depend on how a conversion treats a
+// signalling NaN.
+__host__ __device__ inline float f32_store(double v) {
+    if (v != v)
+        return __builtin_bit_cast(float, (hiw(v) & 0x80000000u) | 0x7fc00000u | ((hiw(v) & 0x7ffffu) << 3) | (low(v) >> 29));
+    return (float)v;
+}
+
 __host__ __device__ inline double min_(double a, double b) {
     if (isnan_(a) || isnan_(b)) return nan_();
     if (a == 0 && b == 0) return signbit_(a) ? a : b;
@@ -136,7 +146,10 @@ __host__ __device__ inline double log(double x) {
     const uint32_t lx = low(x);
     if (hx < 0x00100000) {
         if (((hx & 0x7fffffff) | lx) == 0) return -__builtin_inf();
-        if (hx < 0) return __builtin_nan("");
+        // V8's ieee754::log returns std::numeric_limits<double>::signaling_NaN() for every argument
+        // with the sign bit set other than -0 (-Inf and a negative NaN included): 0x7ff4000000000000,
+        // which a Float64Array keeps and a Float32Array store quiets to 0x7fe00000 (f32_store)
+        if (hx < 0) return mkd(0x7ff40000u, 0u);
         k -= 54;
         x *= two54;
         hx = (int32_t)hiw(x);

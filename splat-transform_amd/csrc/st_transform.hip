@@ -64,7 +64,9 @@ __global__ __launch_bounds__(256) void k_transform(const TransformArgs a) {
 #pragma unroll
             for (int c = 0; c < 3; ++c) {
                 const double v = a.scale[c][i];
-                a.scale[c][i] = (float)js::x86_nan(js::log(js::exp(v) * a.s), v != v);
+                // Math.log of exp(v) * s: an invalid product (Inf * 0) is x86's negative NaN, and
+                // js::log answers a negative argument as V8 does
+                a.scale[c][i] = js::f32_store(js::log(js::x86_nan(js::exp(v) * a.s, v != v || a.s != a.s)));
             }
         }
         if (C > 0) {
@@ -148,7 +150,7 @@ __global__ __launch_bounds__(256) void k_transform_t(const TransformArgsT a) {
 #pragma unroll
             for (int c = 0; c < 3; ++c) {
                 const double v = ta_load(a.scale[c].p, a.scale[c].t, i);
-                ta_store(a.scale[c].p, a.scale[c].t, i, js::x86_nan(js::log(js::exp(v) * a.s), v != v));
+                ta_store(a.scale[c].p, a.scale[c].t, i, js::log(js::x86_nan(js::exp(v) * a.s, v != v || a.s != a.s)));
             }
         }
         if (C > 0) {

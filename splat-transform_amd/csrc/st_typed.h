@@ -35,7 +35,7 @@ __host__ __device__ inline void ta_store(void *p, int32_t t, uint64_t i, double 
         case ST_PLY_USHORT: static_cast<uint16_t *>(p)[i] = (uint16_t)js::to_uint32(v); break;
         case ST_PLY_INT: static_cast<int32_t *>(p)[i] = js::to_int32(v); break;
         case ST_PLY_UINT: static_cast<uint32_t *>(p)[i] = js::to_uint32(v); break;
-        case ST_PLY_FLOAT: static_cast<float *>(p)[i] = (float)v; break;
+        case ST_PLY_FLOAT: static_cast<float *>(p)[i] = js::f32_store(v); break;
         default: static_cast<double *>(p)[i] = v; break;
     }
 }

@@ -51,19 +51,26 @@ def _table(n, C, seed, spice=False):
     return cols
 
 
-@pytest.mark.parametrize('n', [0, 1, 2, 3, 255, 256, 257, 1023, 1025])
-def test_morton_ragged_vs_oracle(ctx, n):
+RAGGED_N = [0, 1, 2, 3, 255, 256, 257, 1023, 1025]
+DEGENERATE_CASES = ['all_equal', 'nan_coords', 'inf_extent', 'one_axis_flat', 'big_equal_run',
+                    'neg_zero', 'lattice', 'blobs', 'blobs_flat', 'clumps', 'clumps_dup']
+ONESWEEP_N = [2048, 2049, 4095, 65535, 65536, 65537, 4096 * 25 + 1, 4096 * 37, 1_500_007]
+
+
+def morton_ragged_case(n):
     rng = np.random.default_rng(n)
-    x, y, z = (rng.normal(0, 5, n).astype(np.float32) for _ in range(3))
+    return tuple(rng.normal(0, 5, n).astype(np.float32) for _ in range(3))
+
+
+@pytest.mark.parametrize('n', RAGGED_N)
+def test_morton_ragged_vs_oracle(ctx, n):
+    x, y, z = morton_ragged_case(n)
     same_bits(ctx.morton_order(x, y, z), oracle.morton_order(x, y, z))
 
 
-@pytest.mark.parametrize('case', ['all_equal', 'nan_coords', 'inf_extent', 'one_axis_flat', 'big_equal_run',
-                                  'neg_zero', 'lattice', 'blobs', 'blobs_flat', 'clumps', 'clumps_dup'])
-@pytest.mark.parametrize('n', [5000, 70001, 1_000_003])
-def test_morton_degenerate_vs_oracle(ctx, case, n):
-    """ordering.ts:53-65: zero-length extents, non-finite extents (ordering skipped), NaN
-    coordinates (key 0), equal-key runs longer than 256 (recursion with their own extents)."""
+def morton_degenerate_case(case, n):
+    """the float32 positions of test_morton_degenerate_vs_oracle (shared with the typed-column
+    tests, which run them through other column types)"""
     rng = np.random.default_rng(7)
     x, y, z = (rng.normal(0, 5, n).astype(np.float32) for _ in range(3))
     if case == 'all_equal':
@@ -106,20 +113,34 @@ def test_morton_degenerate_vs_oracle(ctx, case, n):
         if case == 'clumps_dup':
             half = m & (rng.random(n) < 0.5)
             x[half] += np.float32(1e-4)
+    return x, y, z
+
+
+@pytest.mark.parametrize('case', DEGENERATE_CASES)
+@pytest.mark.parametrize('n', [5000, 70001, 1_000_003])
+def test_morton_degenerate_vs_oracle(ctx, case, n):
+    """ordering.ts:53-65: zero-length extents, non-finite extents (ordering skipped), NaN
+    coordinates (key 0), equal-key runs longer than 256 (recursion with their own extents)."""
+    x, y, z = morton_degenerate_case(case, n)
     same_bits(ctx.morton_order(x, y, z), oracle.morton_order(x, y, z))
 
 
-@pytest.mark.parametrize('n', [2048, 2049, 4095, 65535, 65536, 65537, 4096 * 25 + 1, 4096 * 37, 1_500_007])
-def test_morton_onesweep_sizes_vs_oracle(ctx, n):
-    """Level-0 sorts of whole and ragged 4,096-key tiles, and a caller-supplied permutation of
-    the indices (the values carried through the passes are idx[j]: ordering.ts:4-20 sorts the
-    indices it is given)."""
+def morton_onesweep_case(n):
     rng = np.random.default_rng(n)
     x, y, z = (rng.normal(0, 10, n).astype(np.float32) for _ in range(3))
     m = rng.random(n) < 0.05
     for a in (x, y, z):
         a[m] = (2 + rng.random(m.sum()) * 1e-3).astype(np.float32)
     perm = rng.permutation(n).astype(np.uint32)
+    return x, y, z, perm
+
+
+@pytest.mark.parametrize('n', ONESWEEP_N)
+def test_morton_onesweep_sizes_vs_oracle(ctx, n):
+    """Level-0 sorts of whole and ragged 4,096-key tiles, and a caller-supplied permutation of
+    the indices (the values carried through the passes are idx[j]: ordering.ts:4-20 sorts the
+    indices it is given)."""
+    x, y, z, perm = morton_onesweep_case(n)
     same_bits(ctx.morton_order(x, y, z, perm), oracle.morton_order(x, y, z, perm))
     same_bits(ctx.morton_order(x, y, z), oracle.morton_order(x, y, z))
 
@@ -142,7 +163,12 @@ def test_morton_index_subsets_vs_oracle(ctx, n, m):
     same_bits(tidx.cpu().numpy().view(np.uint32), oracle.morton_order(x, y, z, idx))
 
 
-@pytest.mark.parametrize('n,C', [(1, 0), (255, 3), (256, 15), (257, 8), (1000, 15), (4097, 3)])
+PACK_EDGES = [(1, 0), (255, 3), (256, 15), (257, 8), (1000, 15), (4097, 3)]
+TRANSFORM_EXTREMES = [('scale', 0.0), ('scale', 1e30), ('translate', (1e38, -1e38, 0.0)),
+                      ('rotate', (90, 0, 180)), ('rotate', (0.0, 0.0, 0.0))]
+
+
+@pytest.mark.parametrize('n,C', PACK_EDGES)
 def test_pack_compressed_edges_vs_oracle(ctx, n, C):
     """compressed-chunk.ts:44-180: NaN-propagating chunk min/max, the +-20 scale clamp, zero
     quaternions, the padded last chunk (write-compressed-ply.ts:90-93), SH byte saturation."""
@@ -191,8 +217,7 @@ def test_filter_finite_edges_vs_oracle(ctx, kind):
     same_bits(np.asarray(got, np.uint32), np.asarray(want, np.uint32))
 
 
-@pytest.mark.parametrize('action', [('scale', 0.0), ('scale', 1e30), ('translate', (1e38, -1e38, 0.0)),
-                                    ('rotate', (90, 0, 180)), ('rotate', (0.0, 0.0, 0.0))])
+@pytest.mark.parametrize('action', TRANSFORM_EXTREMES)
 def test_transform_extremes_vs_oracle(ctx, action):
     """transform.ts:12-65 with a zero / huge scale (log(0) = -inf, overflow), huge
     translations and exact-angle rotations over NaN / Inf / -0 inputs."""
