@@ -58,6 +58,9 @@
  *   st_compressed_ply / st_dev_...          processDataTable + writeCompressedPly
  *                                           (CLI: in.ply [actions] out.compressed.ply) index.ts:463-496,
  *                                                                               write-compressed-ply.ts:31-115
+ *   st_dev_csv_rows / st_dev_csv_file /     writeCsv (header line, rows of
+ *   st_csv_file / st_ply_csv_file             Number::toString cells)            writers/write-csv.ts:5-23,
+ *                                                                               index.ts:117-118
  *
  * Conventions
  *  - Columns are SoA float32 arrays of n rows (the reference's Float32Array
@@ -610,6 +613,46 @@ int st_ply_file(st_ctx *ctx, const st_ttable *src, const st_action *actions, int
 int st_ply_ply_file(st_ctx *ctx, int32_t fd, const st_ply_header *h, int32_t element, const st_action *actions,
                     int32_t nactions, const char *const *comments, int32_t ncomments, int32_t out_fd,
                     uint64_t *out_m, uint64_t *size);
+
+/* ---- the CSV writer (writers/write-csv.ts, the 'csv' case of index.ts:117-118) ----
+ * The file is the header line -- the column names joined by ',' and a '\n', written raw (no
+ * quoting: write-csv.ts:9-10) -- and per row the cells '' + column[i] joined by ',' and a '\n'
+ * (write-csv.ts:15-22).  A cell is ECMA-262 Number::toString of the element as a JS number: an
+ * integer column's plain decimal; a float32 widened exactly to a double first (0.1f is
+ * 0.10000000149011612); the shortest digits that round back to the double, the closest among
+ * those, fixed up to 21 digits and down to 1e-6, exponent form outside (1e+21, 1e-7); NaN,
+ * Infinity, -Infinity, 0 for both zeros.  At most 25 bytes.
+ * st_csv_max_row_bytes (host only, no context): the longest row the table's types admit -- per
+ * column the longest cell of its type (4 3 6 5 11 10 25 25 in st_ply_type order) plus one
+ * separator; 0 for a bad table.  Rows above 48 KiB by this bound (more than 1,890 float64
+ * columns) are ST_ERR_UNSUPPORTED in every call below.
+ * st_csv_header_text (host only): the header line; malloc'd (st_free), *size excludes the NUL.
+ * A table without columns is ST_ERR_ARG here and below (the reference's DataTable refuses it).
+ * st_dev_csv_rows: the kernels alone -- the text of rows [row0, row0 + nrows) of a device table of
+ * any column types, contiguous at dev_out (device, 4-byte aligned).  *size = the bytes the rows
+ * need; above cap the call returns ST_ERR_ARG and writes nothing.  No byte outside
+ * [dev_out, dev_out + *size) is written.  The call returns once the size is known; the text is
+ * complete in stream order.
+ * st_dev_csv_file: header + all rows of a device table written to out_fd from its position.  The
+ * rows become text a piece at a time (as many rows as fit one pinned slot by the worst-case
+ * width) in two device staging buffers and come down through st_compressed_ply_file's pinned
+ * slots while a host thread writes the slot before; the whole text never exists in HBM.
+ * out_fd as for st_compressed_ply_file: seekable, open for writing, not O_APPEND (ST_ERR_ARG
+ * before any work); its position ends after the output and a longer file is cut there.
+ * st_csv_file: processDataTable on a host table (uploaded once), then header + rows.  *out_m =
+ * the processed table's rows, *size = the bytes written.
+ * st_ply_csv_file: the CLI's `in.ply [actions] out.csv` -- the element's rows stay resident from
+ * the file to the text; element < 0 selects the element named "vertex".
+ * One device writes: the st_set_devices group is not used by these calls. */
+uint64_t st_csv_max_row_bytes(const st_ttable *t);
+int st_csv_header_text(const st_ttable *t, char **out, uint64_t *size);
+int st_dev_csv_rows(st_ctx *ctx, const st_ttable *dev_table, uint64_t row0, uint64_t nrows, uint8_t *dev_out,
+                    uint64_t cap, uint64_t *size);
+int st_dev_csv_file(st_ctx *ctx, const st_ttable *dev_table, int32_t out_fd, uint64_t *size);
+int st_csv_file(st_ctx *ctx, const st_ttable *src, const st_action *actions, int32_t nactions, int32_t out_fd,
+                uint64_t *out_m, uint64_t *size);
+int st_ply_csv_file(st_ctx *ctx, int32_t fd, const st_ply_header *h, int32_t element, const st_action *actions,
+                    int32_t nactions, int32_t out_fd, uint64_t *out_m, uint64_t *size);
 
 /* ---- the other input formats: .splat, .ksplat, .spz (index.ts:52-76) ----------
  * Each reader decodes packed per-splat records into 14 + nsh float32 columns in its own order:

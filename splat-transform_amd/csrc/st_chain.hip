@@ -444,6 +444,48 @@ uint64_t ply_chain_to_file(Chain &ch, const char *const *comments, int ncomments
     return total - base;
 }
 
+// writeCsv's rows (write-csv.ts:15-22) of a device table to fd at file offset `off`: a piece is as
+// many rows as fit one ring slot by the worst-case row width; its length pass and scan run first
+// and its byte count is read back (submit() needs it and the next piece's file offset), then the
+// text goes into one of two device staging buffers and down through the ring while the writer
+// thread writes the slot before.  Returns the bytes written.
+uint64_t csv_rows_to_file(st_ctx *c, CsvRows &cr, const st_ttable *t, int fd, uint64_t off) {
+    if (!t->n) return 0;
+    FileRing ring(c, fd);
+    const uint64_t piece_rows = cr.piece_rows(std::min<uint64_t>(ring.slot, CSV_PIECE_BYTES));
+    const uint64_t stage_bytes = piece_rows * cr.W + 8;
+    uint8_t *stage[2] = {wsT<uint8_t>(c, "csvw.stage0", stage_bytes), wsT<uint8_t>(c, "csvw.stage1", stage_bytes)};
+    uint64_t done = 0;
+    try {
+        int k = 0;
+        for (uint64_t row = 0; row < t->n; row += piece_rows, ++k) {
+            const uint64_t nr = std::min(piece_rows, t->n - row);
+            const uint64_t nb = cr.measure(row, nr);
+            uint8_t *host = ring.next();
+            if (!host) break;
+            cr.write(row, nr, stage[k & 1], 0);
+            ST_HIP(hipMemcpyAsync(host, stage[k & 1], nb, hipMemcpyDeviceToHost, c->stream));
+            ring.submit(nb, off + done);
+            done += nb;
+        }
+    } catch (...) {
+        ring.fail(std::current_exception());
+    }
+    ring.finish();
+    return done;
+}
+
+// header + rows of a device table to out_fd from its position (writeCsv, index.ts:117-118)
+uint64_t csv_table_to_file(st_ctx *c, const st_ttable *t, int fd) {
+    const std::string head = csv_header_text(t);
+    const uint64_t base = file_base(fd, "csv file");
+    CsvRows cr(c, t, "csvw");  // the table's own errors before the first byte is written
+    write_at(fd, reinterpret_cast<const uint8_t *>(head.data()), head.size(), base);
+    const uint64_t total = base + head.size() + csv_rows_to_file(c, cr, t, fd, base + head.size());
+    file_end(fd, total, "csv file");
+    return total - base;
+}
+
 // the host table into the chain
 auto host_loader(st_ctx *c, const st_ttable *src) {
     return [=](Chain &ch) {
@@ -729,6 +771,45 @@ int st_ply_ply_file(st_ctx *c, int32_t fd, const st_ply_header *h, int32_t eleme
         ply_chain(c, fd, h, element, ch);
         run_actions(ch, actions, nactions);
         *size = ply_chain_to_file(ch, comments, ncomments, out_fd);
+        *out_m = ch.n;
+    });
+}
+
+int st_dev_csv_file(st_ctx *c, const st_ttable *t, int32_t out_fd, uint64_t *size) {
+    return guard([&] {
+        ST_REQUIRE(c && t && size, ST_ERR_ARG, "NULL argument");
+        check_src(t);
+        sog_file_check(out_fd);
+        use_device(c);
+        *size = csv_table_to_file(c, t, out_fd);
+    });
+}
+
+int st_csv_file(st_ctx *c, const st_ttable *src, const st_action *actions, int32_t nactions, int32_t out_fd,
+                uint64_t *out_m, uint64_t *size) {
+    return guard([&] {
+        ST_REQUIRE(c && src && out_m && size && (actions || nactions == 0), ST_ERR_ARG, "NULL argument");
+        check_src(src);
+        sog_file_check(out_fd);
+        use_device(c);
+        Chain ch{c};
+        upload_chain(c, src, ch);
+        run_actions(ch, actions, nactions);
+        *size = csv_table_to_file(c, ch.typed(), out_fd);
+        *out_m = ch.n;
+    });
+}
+
+int st_ply_csv_file(st_ctx *c, int32_t fd, const st_ply_header *h, int32_t element, const st_action *actions,
+                    int32_t nactions, int32_t out_fd, uint64_t *out_m, uint64_t *size) {
+    return guard([&] {
+        ST_REQUIRE(c && h && fd >= 0 && out_m && size && (actions || nactions == 0), ST_ERR_ARG, "NULL argument");
+        sog_file_check(out_fd);
+        use_device(c);
+        Chain ch{c};
+        ply_chain(c, fd, h, element, ch);
+        run_actions(ch, actions, nactions);
+        *size = csv_table_to_file(c, ch.typed(), out_fd);
         *out_m = ch.n;
     });
 }

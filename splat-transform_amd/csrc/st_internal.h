@@ -423,6 +423,31 @@ struct PlyRows {
 std::string ply_header_text(const st_ttable *t, const char *element, const char *const *comments, int ncomments,
                             bool element_only);
 
+// the CSV writer (write-csv.ts, st_csv.hip): one device table's rows as text, a piece at a time.
+// The constructor checks the table (ST_ERR_ARG: no columns, a bad type, a misaligned column;
+// ST_ERR_UNSUPPORTED: a worst-case row -- every cell at its type's longest text, plus a separator
+// per cell -- above CSV_LDS_BYTES) and uploads its layout and the power-of-ten table.  measure()
+// runs the length pass and the scan over rows [row0, row0 + nrows) and returns their bytes (it
+// waits for the stream); write() then queues the same rows' text at out + out_off (out 4-byte
+// aligned, out_off any byte).  A piece holds at most CSV_PIECE_BYTES by the worst-case width.
+constexpr uint64_t CSV_LDS_BYTES = 48 * 1024, CSV_PIECE_BYTES = 256ull << 20;
+struct CsvRows {
+    st_ctx *c;
+    std::string tag;
+    uint32_t W = 0, RB = 1;  // worst-case row bytes, rows per workgroup: min(256, CSV_LDS_BYTES / W)
+    int ncol = 0;
+    void *d_cols = nullptr;
+    uint64_t *d_tab = nullptr;
+    uint16_t *coff = nullptr;
+    uint32_t *rowoff = nullptr;
+    CsvRows(st_ctx *ctx, const st_ttable *t, const std::string &tag);
+    uint64_t measure(uint64_t row0, uint64_t nrows);
+    void write(uint64_t row0, uint64_t nrows, uint8_t *out, uint64_t out_off);
+    uint64_t piece_rows(uint64_t bytes) const;  // the rows that fit `bytes` whatever their values
+};
+uint64_t csv_max_row_bytes(const st_ttable *t);
+std::string csv_header_text(const st_ttable *t);  // write-csv.ts:9-10
+
 // multi-GPU building blocks (st_dist.hip)
 void minmax_dev(st_ctx *c, const float *const *cols, int ncols, uint64_t n, double *lo, double *hi);
 void dist_prepare(st_ctx *c, const float *const *cols, int d, uint64_t n);

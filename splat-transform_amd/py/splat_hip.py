@@ -126,6 +126,8 @@ EXPORTS = [
     'st_dev_spz_read',
     'st_ply_header_text', 'st_ply_element_text', 'st_dev_ply_rows', 'st_dev_ply_rows_file', 'st_ply_rows_file',
     'st_ply_file', 'st_ply_ply_file',
+    'st_csv_max_row_bytes', 'st_csv_header_text', 'st_dev_csv_rows', 'st_dev_csv_file', 'st_csv_file',
+    'st_ply_csv_file',
 ]
 
 
@@ -158,9 +160,10 @@ def lib():
         L.st_free.restype = None
         L.st_webp_max_size.restype = ctypes.c_uint64
         L.st_ply_row_bytes.restype = ctypes.c_uint64
+        L.st_csv_max_row_bytes.restype = ctypes.c_uint64
         for name in EXPORTS:
             if name not in ('st_last_error', 'st_ctx_last_timings', 'st_ctx_last_kmeans_stats', 'st_ctx_destroy', 'st_free', 'st_webp_max_size',
-                            'st_ply_row_bytes', 'st_comm_destroy', 'st_group_destroy'):
+                            'st_ply_row_bytes', 'st_csv_max_row_bytes', 'st_comm_destroy', 'st_group_destroy'):
                 getattr(L, name).restype = ctypes.c_int
         _lib = L
     return _lib
@@ -554,6 +557,23 @@ def ply_header_text(schema, n, element=None, comments=(), element_only=False):
         cs, nc = _comments_arg(comments)
         check(lib().st_ply_header_text(ctypes.byref(t), el, cs, nc, ctypes.byref(out), ctypes.byref(size)))
     return _take(out, size)
+
+
+def csv_header_text(cols):
+    """writeCsv's header line (write-csv.ts:9-10): the column names joined by ',' and a newline, raw.
+    cols: a list of (name, numpy dtype or array) or a dict.  Host only -> bytes"""
+    items = list(cols.items()) if isinstance(cols, dict) else list(cols)
+    t = _schema_ttable(items, 0)
+    out, size = ctypes.c_void_p(), ctypes.c_uint64(0)
+    check(lib().st_csv_header_text(ctypes.byref(t), ctypes.byref(out), ctypes.byref(size)))
+    return _take(out, size)
+
+
+def csv_max_row_bytes(cols):
+    """the longest row of text the columns' types admit (st_csv_max_row_bytes): per column its type's
+    longest cell plus one separator.  Host only"""
+    items = list(cols.items()) if isinstance(cols, dict) else list(cols)
+    return lib().st_csv_max_row_bytes(ctypes.byref(_schema_ttable(items, 0)))
 
 
 class _OutFd:
@@ -1359,6 +1379,57 @@ class Context:
                 check(lib().st_ply_ply_file(self.h, ctypes.c_int32(fd), ctypes.byref(h), ctypes.c_int32(element), acts,
                                             ctypes.c_int32(len(actions)), cs, nc, ofd, ctypes.byref(m),
                                             ctypes.byref(size)))
+        finally:
+            os.close(fd)
+        return m.value, size.value
+
+    # ---- writeCsv (write-csv.ts) ---------------------------------------------------------
+    def dev_csv_rows(self, cols, out, row0=0, nrows=None):
+        """st_dev_csv_rows: the text of rows [row0, row0 + nrows) of device columns (list of (name,
+        tensor) or a dict, any types) at `out`, a device uint8 tensor -> the bytes written.  A tensor
+        too small for them raises ST_ERR_ARG and is left untouched"""
+        t = make_ttable(cols)
+        if nrows is None:
+            nrows = t.n - row0
+        size = ctypes.c_uint64()
+        check(lib().st_dev_csv_rows(self.h, ctypes.byref(t), ctypes.c_uint64(row0), ctypes.c_uint64(nrows), _ptr(out),
+                                    ctypes.c_uint64(out.numel()), ctypes.byref(size)))
+        return size.value
+
+    def dev_csv_file(self, cols, out):
+        """writeCsv (write-csv.ts:5-23) of a table already in HBM (list of (name, tensor) or a dict)
+        into `out`, a path or a descriptor (written from its position) -> bytes written"""
+        t = make_ttable(cols)
+        size = ctypes.c_uint64()
+        with _OutFd(out) as fd:
+            check(lib().st_dev_csv_file(self.h, ctypes.byref(t), fd, ctypes.byref(size)))
+        return size.value
+
+    def csv_file(self, cols, actions, out):
+        """processDataTable + writeCsv of a host table (list of (name, numpy array) or a dict) into
+        `out`, a path or a descriptor (st_csv_file): (rows written, file bytes).  The input arrays are
+        not changed"""
+        items = list(cols.items()) if isinstance(cols, dict) else list(cols)
+        ts = make_ttable(items, len(items[0][1]) if items else 0)
+        acts = make_actions(actions)
+        m, size = ctypes.c_uint64(), ctypes.c_uint64()
+        with _OutFd(out) as fd:
+            check(lib().st_csv_file(self.h, ctypes.byref(ts), acts, ctypes.c_int32(len(actions)), fd,
+                                    ctypes.byref(m), ctypes.byref(size)))
+        return m.value, size.value
+
+    def ply_csv_file(self, path, actions, out, element=-1):
+        """the CLI's `in.ply [actions] out.csv` (st_ply_csv_file): the element's rows stay in HBM from
+        ingest to output: (rows written, file bytes)"""
+        fd = os.open(path, os.O_RDONLY)
+        try:
+            h = PlyHeader()
+            check(lib().st_ply_read_header(ctypes.c_int32(fd), ctypes.byref(h)))
+            acts = make_actions(actions)
+            m, size = ctypes.c_uint64(), ctypes.c_uint64()
+            with _OutFd(out) as ofd:
+                check(lib().st_ply_csv_file(self.h, ctypes.c_int32(fd), ctypes.byref(h), ctypes.c_int32(element), acts,
+                                            ctypes.c_int32(len(actions)), ofd, ctypes.byref(m), ctypes.byref(size)))
         finally:
             os.close(fd)
         return m.value, size.value
