@@ -654,6 +654,62 @@ int st_csv_file(st_ctx *ctx, const st_ttable *src, const st_action *actions, int
 int st_ply_csv_file(st_ctx *ctx, int32_t fd, const st_ply_header *h, int32_t element, const st_action *actions,
                     int32_t nactions, int32_t out_fd, uint64_t *out_m, uint64_t *size);
 
+/* ---- the HTML viewer writer (writers/write-html.ts, the 'html' case of index.ts:135-143) ----
+ * The file is the viewer's page with its style link, its script tag and its settings fetch
+ * replaced by the inlined css, js and JSON.stringify(experienceSettings), and fetch(contentUrl)
+ * by fetch("data:application/ply;base64,<text>") where <text> is the RFC 4648 base64 (A-Z a-z 0-9
+ * + /, '=' padding: Buffer.toString('base64')) of the .compressed.ply file of the table.  The
+ * viewer template (html, css, js: @playcanvas/supersplat-viewer's exports) is the caller's; all
+ * text is UTF-8, NUL-terminated.
+ * st_base64_size (host only, no context): 4 * ceil(nbytes / 3).
+ * st_dev_base64: the kernel alone.  segs (at most 4, device pointers, any alignment, a length may
+ * be 0) make one byte stream back to back; the text of its bytes [byte0, byte0 + nbytes) is
+ * written contiguously at dev_out (device, 4-byte aligned) on the context stream.  byte0 is a
+ * multiple of 3; nbytes is a multiple of 3 unless the range ends the stream, where the padding
+ * goes.  *size = st_base64_size(nbytes); above cap, for a misaligned dev_out and for a range
+ * outside these rules the call returns ST_ERR_ARG and writes nothing.  No byte outside
+ * [dev_out, dev_out + *size) is written.
+ * st_html_parts (host only): write-html.ts:11-14,24-36,46-55.  pad(text, 12) puts 12 spaces
+ * before every '\n'-separated line, empty ones too.  The settings are JSON.stringify's text in
+ * the reference's key order: {"camera":{"fov":50,"position":[..],"target":[..],"startAnim":"none"},
+ * "background":{"color":[0.4,0.4,0.4]},"animTracks":[]}; a number is Number::toString (the CSV
+ * writer's digits), null when not finite, 0 for -0.  The replaces run in order, each on the result
+ * of the one before, as String.prototype.replace with a string pattern: the first occurrence
+ * only, a missing pattern changes nothing, and in the inserted text $$ is '$', $& the pattern, $`
+ * the text before the match and $' the text after it; every other '$' stays.  The page is
+ * returned split around the payload: *prefix ends with fetch("data:application/ply;base64, and
+ * *suffix begins with ").  Without a fetch(contentUrl) *embeds = 0, *prefix is the whole page and
+ * *suffix is empty.  Both are malloc'd (st_free); the sizes exclude the NUL.  camera / target: 3
+ * doubles each.
+ * st_html_file / st_ply_html_file: the chain of st_compressed_ply_file /
+ * st_ply_compressed_ply_file (the actions, the Morton order, the chunk pack; the same errors, the
+ * same *out_m / *out_sh_coeffs), then prefix + base64(header | chunk | vertex | sh) + suffix
+ * written from out_fd's position.  The compressed file never exists on the host: the arrays stay
+ * in HBM, the text is made a piece at a time (one pinned slot of text from slot / 4 * 3 stream
+ * bytes) in two device staging buffers and comes down through st_compressed_ply_file's pinned
+ * slots while a host thread writes the slot before.  Without a fetch(contentUrl) the chain still
+ * runs (its errors surface, as the reference still runs writeCompressedPly) and the page alone is
+ * written.  out_fd as for st_compressed_ply_file: seekable, open for writing, not O_APPEND
+ * (ST_ERR_ARG before any work); its position ends after the output and a longer file is cut
+ * there.  *size = the bytes written.  version as for st_compressed_ply_file.
+ * One device writes: the st_set_devices group is not used by these calls. */
+typedef struct st_bytes_seg {
+    const uint8_t *ptr;
+    uint64_t len;
+} st_bytes_seg;
+uint64_t st_base64_size(uint64_t nbytes);
+int st_dev_base64(st_ctx *ctx, const st_bytes_seg *segs, int32_t nseg, uint64_t byte0, uint64_t nbytes,
+                  uint8_t *dev_out, uint64_t cap, uint64_t *size);
+int st_html_parts(const char *html, const char *css, const char *js, const double *camera, const double *target,
+                  char **prefix, uint64_t *prefix_size, char **suffix, uint64_t *suffix_size, int32_t *embeds);
+int st_html_file(st_ctx *ctx, const st_ttable *src, const st_action *actions, int32_t nactions, const char *html,
+                 const char *css, const char *js, const double *camera, const double *target, int32_t out_fd,
+                 const char *version, uint64_t *out_m, int32_t *out_sh_coeffs, uint64_t *size);
+int st_ply_html_file(st_ctx *ctx, int32_t fd, const st_ply_header *h, int32_t element, const st_action *actions,
+                     int32_t nactions, const char *html, const char *css, const char *js, const double *camera,
+                     const double *target, int32_t out_fd, const char *version, uint64_t *out_m,
+                     int32_t *out_sh_coeffs, uint64_t *size);
+
 /* ---- the other input formats: .splat, .ksplat, .spz (index.ts:52-76) ----------
  * Each reader decodes packed per-splat records into 14 + nsh float32 columns in its own order:
  * x y z scale_0..2 f_dc_0..2 opacity rot_0..3 f_rest_0..nsh-1 (nsh = 0, 9, 24 or 45).

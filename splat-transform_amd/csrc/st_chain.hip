@@ -365,26 +365,36 @@ void file_end(int fd, uint64_t total, const char *what) {
     ST_REQUIRE(lseek(fd, (off_t)total, SEEK_SET) == (off_t)total, ST_ERR_ARG, std::string(what) + ": lseek failed");
 }
 
-// the device arrays to fd at offsets from its position through the ring; the file ends at the last byte
-uint64_t compressed_ply_to_file(st_ctx *c, uint64_t m, int C, const float *dchunk, const uint32_t *dvert,
-                                const uint8_t *dsh, int fd, const char *version) {
-    const std::string head = compressed_ply_header(m, C, version);
-    const uint64_t base = file_base(fd, "compressed ply file");
-    write_at(fd, reinterpret_cast<const uint8_t *>(head.data()), head.size(), base);
+// what follows the header in a .compressed.ply file (write-compressed-ply.ts:112-114): the chunk,
+// vertex and sh arrays in HBM, in file order, the empty ones left out; `off` = a region's first
+// byte counted from the header's end
+struct Region {
+    const uint8_t *dev;
+    uint64_t bytes, off;
+};
+std::vector<Region> compressed_ply_regions(uint64_t m, int C, const float *dchunk, const uint32_t *dvert,
+                                           const uint8_t *dsh) {
     const uint64_t nch = (m + 255) / 256;
-    struct Region {
-        const uint8_t *dev;
-        uint64_t bytes, off;
-    };
     std::vector<Region> rs;
-    uint64_t off = base + head.size();
+    uint64_t off = 0;
     for (const Region &r : {Region{reinterpret_cast<const uint8_t *>(dchunk), nch * 72, 0},
                             Region{reinterpret_cast<const uint8_t *>(dvert), m * 16, 0},
                             Region{dsh, C ? m * 3 * (uint64_t)C : 0, 0}}) {
         if (r.bytes) rs.push_back({r.dev, r.bytes, off});
         off += r.bytes;
     }
-    const uint64_t total = off;
+    return rs;
+}
+
+// the device arrays to fd at offsets from its position through the ring; the file ends at the last byte
+uint64_t compressed_ply_to_file(st_ctx *c, uint64_t m, int C, const float *dchunk, const uint32_t *dvert,
+                                const uint8_t *dsh, int fd, const char *version) {
+    const std::string head = compressed_ply_header(m, C, version);
+    const uint64_t base = file_base(fd, "compressed ply file");
+    write_at(fd, reinterpret_cast<const uint8_t *>(head.data()), head.size(), base);
+    const std::vector<Region> rs = compressed_ply_regions(m, C, dchunk, dvert, dsh);
+    const uint64_t body = base + head.size();
+    const uint64_t total = body + (rs.empty() ? 0 : rs.back().off + rs.back().bytes);
     FileRing ring(c, fd);
     try {
         bool ok = true;
@@ -394,7 +404,7 @@ uint64_t compressed_ply_to_file(st_ctx *c, uint64_t m, int C, const float *dchun
                 uint8_t *host = ring.next();
                 if (!(ok = host != nullptr)) break;
                 ST_HIP(hipMemcpyAsync(host, rs[i].dev + o, nb, hipMemcpyDeviceToHost, c->stream));
-                ring.submit(nb, rs[i].off + o);
+                ring.submit(nb, body + rs[i].off + o);
             }
     } catch (...) {
         ring.fail(std::current_exception());
@@ -402,6 +412,69 @@ uint64_t compressed_ply_to_file(st_ctx *c, uint64_t m, int C, const float *dchun
     ring.finish();
     file_end(fd, total, "compressed ply file");
     return total - base;
+}
+
+// writeHtml's file (write-html.ts:51-57) to fd from its position: the page's prefix, the base64 text
+// of header | chunk | vertex | sh, its suffix.  The compressed file is a virtual stream over the
+// header (uploaded) and the arrays where compressed_tail left them; a piece is one ring slot of text
+// (slot / 4 * 3 stream bytes) encoded into one of two device staging buffers, then copied into the
+// slot while the writer thread writes the slot before.  A page without fetch(contentUrl) is written
+// alone.
+uint64_t html_to_file(st_ctx *c, const HtmlParts &page, uint64_t m, int C, const float *dchunk,
+                      const uint32_t *dvert, const uint8_t *dsh, int fd, const char *version) {
+    const uint64_t base = file_base(fd, "html file");
+    write_at(fd, reinterpret_cast<const uint8_t *>(page.prefix.data()), page.prefix.size(), base);
+    uint64_t total = base + page.prefix.size();
+    if (page.embeds) {
+        const std::string head = compressed_ply_header(m, C, version);
+        auto *dhead = wsT<uint8_t>(c, "htmlw.head", head.size());
+        ST_HIP(hipMemcpyAsync(dhead, head.data(), head.size(), hipMemcpyHostToDevice, c->stream));
+        ST_HIP(hipStreamSynchronize(c->stream));  // (head is pageable and leaves with this scope)
+        std::vector<st_bytes_seg> segs{{dhead, head.size()}};
+        uint64_t bytes = head.size();
+        for (const Region &r : compressed_ply_regions(m, C, dchunk, dvert, dsh)) {
+            segs.push_back({r.dev, r.bytes});
+            bytes += r.bytes;
+        }
+        FileRing ring(c, fd);
+        const uint64_t piece = ring.slot / 4 * 3;  // a multiple of 3: the slot is whole MiB
+        uint8_t *stage[2] = {wsT<uint8_t>(c, "htmlw.stage0", ring.slot), wsT<uint8_t>(c, "htmlw.stage1", ring.slot)};
+        try {
+            int k = 0;
+            for (uint64_t b = 0; b < bytes; b += piece, ++k) {
+                const uint64_t nb = std::min(piece, bytes - b), nt = base64_size(nb);
+                uint8_t *host = ring.next();
+                if (!host) break;
+                base64_dev(c, segs.data(), (int)segs.size(), b, nb, stage[k & 1]);
+                ST_HIP(hipMemcpyAsync(host, stage[k & 1], nt, hipMemcpyDeviceToHost, c->stream));
+                ring.submit(nt, total + b / 3 * 4);
+            }
+        } catch (...) {
+            ring.fail(std::current_exception());
+        }
+        ring.finish();
+        total += base64_size(bytes);
+        write_at(fd, reinterpret_cast<const uint8_t *>(page.suffix.data()), page.suffix.size(), total);
+        total += page.suffix.size();
+    }
+    file_end(fd, total, "html file");
+    return total - base;
+}
+
+// the compressed-PLY arrays of the chain's table (workspace slots of st_compressed_ply_file), then
+// the page around their text
+void html_chain_to_file(Chain &ch, const HtmlParts &page, int fd, const char *version, uint64_t *out_m,
+                        int32_t *out_sh_coeffs, uint64_t *size) {
+    st_ctx *c = ch.c;
+    const uint64_t m = ch.n, nch = (m + 255) / 256;
+    auto *dchunk = wsT<float>(c, "chain.chunk", nch * 18);
+    auto *dvert = wsT<uint32_t>(c, "chain.vert", m * 4);
+    auto *dsh = wsT<uint8_t>(c, "chain.sh", m * 3 * (uint64_t)ch.coeffs() + 1);
+    int32_t C = 0;
+    compressed_tail(ch, dchunk, dvert, dsh, &C);
+    *size = html_to_file(c, page, m, C, dchunk, dvert, dsh, fd, version);
+    *out_m = m;
+    *out_sh_coeffs = C;
 }
 
 // writePly's rows (write-ply.ts:37-67) of a device table to fd at file offset `off`: rows are
@@ -714,6 +787,40 @@ int st_compressed_ply_file(st_ctx *c, const st_ttable *src, const st_action *act
         *size = compressed_ply_to_file(c, m, C, dchunk, dvert, dsh, out_fd, version);
         *out_m = m;
         *out_sh_coeffs = C;
+    });
+}
+
+int st_html_file(st_ctx *c, const st_ttable *src, const st_action *actions, int32_t nactions, const char *html,
+                 const char *css, const char *js, const double *camera, const double *target, int32_t out_fd,
+                 const char *version, uint64_t *out_m, int32_t *out_sh_coeffs, uint64_t *size) {
+    return guard([&] {
+        ST_REQUIRE(c && src && out_m && out_sh_coeffs && size && (actions || nactions == 0), ST_ERR_ARG,
+                   "NULL argument");
+        const HtmlParts page = html_parts(html, css, js, camera, target);
+        check_src(src);
+        sog_file_check(out_fd);
+        use_device(c);
+        Chain ch{c};
+        upload_chain(c, src, ch);
+        run_actions(ch, actions, nactions);
+        html_chain_to_file(ch, page, out_fd, version, out_m, out_sh_coeffs, size);
+    });
+}
+
+int st_ply_html_file(st_ctx *c, int32_t fd, const st_ply_header *h, int32_t element, const st_action *actions,
+                     int32_t nactions, const char *html, const char *css, const char *js, const double *camera,
+                     const double *target, int32_t out_fd, const char *version, uint64_t *out_m,
+                     int32_t *out_sh_coeffs, uint64_t *size) {
+    return guard([&] {
+        ST_REQUIRE(c && h && fd >= 0 && out_m && out_sh_coeffs && size && (actions || nactions == 0), ST_ERR_ARG,
+                   "NULL argument");
+        const HtmlParts page = html_parts(html, css, js, camera, target);
+        sog_file_check(out_fd);
+        use_device(c);
+        Chain ch{c};
+        ply_chain(c, fd, h, element, ch);
+        run_actions(ch, actions, nactions);
+        html_chain_to_file(ch, page, out_fd, version, out_m, out_sh_coeffs, size);
     });
 }
 

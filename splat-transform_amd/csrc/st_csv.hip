@@ -105,6 +105,8 @@ const uint64_t *host_table() {
 
 }  // namespace
 
+const uint64_t *numfmt_host_table() { return host_table(); }
+
 uint64_t csv_max_row_bytes(const st_ttable *t) {
     ST_REQUIRE(t->ncol >= 0 && (t->ncol == 0 || t->types), ST_ERR_ARG, "csv: bad table");
     uint64_t w = 0;

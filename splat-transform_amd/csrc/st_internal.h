@@ -447,6 +447,24 @@ struct CsvRows {
 };
 uint64_t csv_max_row_bytes(const st_ttable *t);
 std::string csv_header_text(const st_ttable *t);  // write-csv.ts:9-10
+// st_numfmt.h's power-of-ten table on the host (built at first use): 2 * POW10_ENTRIES words
+const uint64_t *numfmt_host_table();
+
+// the HTML viewer writer (write-html.ts, st_html.hip).  base64_dev queues k_base64 on the context
+// stream: the RFC 4648 text of bytes [byte0, byte0 + nbytes) of the stream that up to B64_MAX_SEGS
+// device segments make back to back, contiguous at out (device, 4-byte aligned).  base64_check
+// throws ST_ERR_ARG for a range the kernel does not take (byte0 not a multiple of 3, a range
+// outside the stream, a partial last group before the stream's end) and returns the text's size;
+// base64_dev runs it first.  html_parts: the page of write-html.ts:46-55 split around the payload.
+constexpr int B64_MAX_SEGS = 4;
+uint64_t base64_size(uint64_t nbytes);
+uint64_t base64_check(const st_bytes_seg *segs, int nseg, uint64_t byte0, uint64_t nbytes);
+void base64_dev(st_ctx *c, const st_bytes_seg *segs, int nseg, uint64_t byte0, uint64_t nbytes, uint8_t *out);
+struct HtmlParts {
+    std::string prefix, suffix;  // the file is prefix + base64 + suffix when embeds, else prefix
+    bool embeds = false;
+};
+HtmlParts html_parts(const char *html, const char *css, const char *js, const double *camera, const double *target);
 
 // multi-GPU building blocks (st_dist.hip)
 void minmax_dev(st_ctx *c, const float *const *cols, int ncols, uint64_t n, double *lo, double *hi);

@@ -128,6 +128,7 @@ EXPORTS = [
     'st_ply_file', 'st_ply_ply_file',
     'st_csv_max_row_bytes', 'st_csv_header_text', 'st_dev_csv_rows', 'st_dev_csv_file', 'st_csv_file',
     'st_ply_csv_file',
+    'st_base64_size', 'st_dev_base64', 'st_html_parts', 'st_html_file', 'st_ply_html_file',
 ]
 
 
@@ -161,9 +162,12 @@ def lib():
         L.st_webp_max_size.restype = ctypes.c_uint64
         L.st_ply_row_bytes.restype = ctypes.c_uint64
         L.st_csv_max_row_bytes.restype = ctypes.c_uint64
+        L.st_base64_size.restype = ctypes.c_uint64
+        L.st_base64_size.argtypes = [ctypes.c_uint64]
         for name in EXPORTS:
             if name not in ('st_last_error', 'st_ctx_last_timings', 'st_ctx_last_kmeans_stats', 'st_ctx_destroy', 'st_free', 'st_webp_max_size',
-                            'st_ply_row_bytes', 'st_csv_max_row_bytes', 'st_comm_destroy', 'st_group_destroy'):
+                            'st_ply_row_bytes', 'st_csv_max_row_bytes', 'st_base64_size', 'st_comm_destroy',
+                            'st_group_destroy'):
                 getattr(L, name).restype = ctypes.c_int
         _lib = L
     return _lib
@@ -574,6 +578,32 @@ def csv_max_row_bytes(cols):
     longest cell plus one separator.  Host only"""
     items = list(cols.items()) if isinstance(cols, dict) else list(cols)
     return lib().st_csv_max_row_bytes(ctypes.byref(_schema_ttable(items, 0)))
+
+
+def base64_size(nbytes):
+    """the bytes of the base64 text of nbytes bytes (st_base64_size): 4 * ceil(nbytes / 3).  Host only"""
+    return lib().st_base64_size(nbytes)
+
+
+def _vec3(v):
+    return (ctypes.c_double * 3)(*[float(x) for x in v])
+
+
+def html_parts(html, css, js, camera=(2, 2, -2), target=(0, 0, 0)):
+    """writeHtml's page text (write-html.ts:11-14,24-36,46-55; st_html_parts) around the payload:
+    html / css / js are the viewer template's three strings (str or UTF-8 bytes).  Host only ->
+    (prefix bytes, suffix bytes, embeds): the file is prefix + base64 + suffix; a page without
+    fetch(contentUrl) has embeds 0, the whole page as prefix and an empty suffix"""
+    enc = [t.encode('utf-8') if isinstance(t, str) else bytes(t) for t in (html, css, js)]
+    pre, suf = ctypes.c_void_p(), ctypes.c_void_p()
+    npre, nsuf, embeds = ctypes.c_uint64(0), ctypes.c_uint64(0), ctypes.c_int32(0)
+    check(lib().st_html_parts(enc[0], enc[1], enc[2], _vec3(camera), _vec3(target), ctypes.byref(pre),
+                              ctypes.byref(npre), ctypes.byref(suf), ctypes.byref(nsuf), ctypes.byref(embeds)))
+    return _take(pre, npre), _take(suf, nsuf), embeds.value
+
+
+class BytesSeg(ctypes.Structure):
+    _fields_ = [('ptr', ctypes.c_void_p), ('len', ctypes.c_uint64)]
 
 
 class _OutFd:
@@ -1433,6 +1463,56 @@ class Context:
         finally:
             os.close(fd)
         return m.value, size.value
+
+    # ---- writeHtml (write-html.ts) -------------------------------------------------------
+    def dev_base64(self, segs, out, byte0=0, nbytes=None):
+        """st_dev_base64: the base64 text of bytes [byte0, byte0 + nbytes) of the stream that `segs` (at
+        most four device uint8 tensors, any alignment, possibly empty) make back to back, at `out`, a
+        device uint8 tensor -> the bytes written.  A tensor too small for them, a misaligned one or a
+        range the kernel does not take raises ST_ERR_ARG and `out` is left untouched"""
+        arr = (BytesSeg * max(len(segs), 1))(*[BytesSeg(s.data_ptr() if s.numel() else None, s.numel()) for s in segs])
+        if nbytes is None:
+            nbytes = sum(s.numel() for s in segs) - byte0
+        size = ctypes.c_uint64()
+        check(lib().st_dev_base64(self.h, arr, ctypes.c_int32(len(segs)), ctypes.c_uint64(byte0),
+                                  ctypes.c_uint64(nbytes), ctypes.c_void_p(out.data_ptr()),
+                                  ctypes.c_uint64(out.numel()), ctypes.byref(size)))
+        return size.value
+
+    def html_file(self, cols, actions, template, out, camera=(2, 2, -2), target=(0, 0, 0), version=None):
+        """processDataTable + writeHtml of a host table (list of (name, numpy array) or a dict) into
+        `out`, a path or a descriptor (st_html_file).  template: the viewer's (html, css, js), str or
+        UTF-8 bytes -> (rows embedded, sh_coeffs, file bytes).  The input arrays are not changed"""
+        items = list(cols.items()) if isinstance(cols, dict) else list(cols)
+        ts = make_ttable(items, len(items[0][1]) if items else 0)
+        acts = make_actions(actions)
+        enc = [t.encode('utf-8') if isinstance(t, str) else bytes(t) for t in template]
+        m, C, size = ctypes.c_uint64(), ctypes.c_int32(), ctypes.c_uint64()
+        with _OutFd(out) as fd:
+            check(lib().st_html_file(self.h, ctypes.byref(ts), acts, ctypes.c_int32(len(actions)), enc[0], enc[1],
+                                     enc[2], _vec3(camera), _vec3(target), fd, version.encode() if version else None,
+                                     ctypes.byref(m), ctypes.byref(C), ctypes.byref(size)))
+        return m.value, C.value, size.value
+
+    def ply_html_file(self, path, actions, template, out, camera=(2, 2, -2), target=(0, 0, 0), version=None,
+                      element=-1):
+        """the CLI's `in.ply [actions] out.html` (st_ply_html_file): the element's rows stay in HBM from
+        ingest to the text: (rows embedded, sh_coeffs, file bytes)"""
+        fd = os.open(path, os.O_RDONLY)
+        try:
+            h = PlyHeader()
+            check(lib().st_ply_read_header(ctypes.c_int32(fd), ctypes.byref(h)))
+            acts = make_actions(actions)
+            enc = [t.encode('utf-8') if isinstance(t, str) else bytes(t) for t in template]
+            m, C, size = ctypes.c_uint64(), ctypes.c_int32(), ctypes.c_uint64()
+            with _OutFd(out) as ofd:
+                check(lib().st_ply_html_file(self.h, ctypes.c_int32(fd), ctypes.byref(h), ctypes.c_int32(element), acts,
+                                             ctypes.c_int32(len(actions)), enc[0], enc[1], enc[2], _vec3(camera),
+                                             _vec3(target), ofd, version.encode() if version else None,
+                                             ctypes.byref(m), ctypes.byref(C), ctypes.byref(size)))
+        finally:
+            os.close(fd)
+        return m.value, C.value, size.value
 
     def ply_sog_bundle(self, path, actions, iters, draws, dos_time, dos_date, element=-1):
         """readPly + processDataTable + writeSog to .sog bytes from the file (st_ply_sog_bundle):
