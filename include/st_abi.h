@@ -58,6 +58,10 @@
  *   st_compressed_ply / st_dev_...          processDataTable + writeCompressedPly
  *                                           (CLI: in.ply [actions] out.compressed.ply) index.ts:463-496,
  *                                                                               write-compressed-ply.ts:31-115
+ *   st_zip_index / st_webp_info /           (none: the reference writes SOG and cannot read it)
+ *     st_webp_decode_lossless /               the inverse of writeSog: ZIP index, WebP-lossless
+ *     st_sog_read_layout / st_dev_sog_decode  decode (RFC 9649) and the dequantising kernel;
+ *     / st_sog_read / st_dev_sog_read         rules in "the .sog reader" below       write-sog.ts:162-268,319-348
  *   st_dev_csv_rows / st_dev_csv_file /     writeCsv (header line, rows of
  *   st_csv_file / st_ply_csv_file             Number::toString cells)            writers/write-csv.ts:5-23,
  *                                                                               index.ts:117-118
@@ -752,6 +756,75 @@ int st_ksplat_read(st_ctx *ctx, const uint8_t *data, uint64_t len, float *const 
 int st_dev_ksplat_read(st_ctx *ctx, const uint8_t *data, uint64_t len, float *const *cols);
 int st_spz_read(st_ctx *ctx, const uint8_t *data, uint64_t len, float *const *host_cols);
 int st_dev_spz_read(st_ctx *ctx, const uint8_t *data, uint64_t len, float *const *cols);
+
+/* ---- the .sog reader (no reference counterpart: the reference writes SOG, write-sog.ts:110-370,
+ * and its CLI at this version cannot read it back) -------------------------------------------
+ * A .sog is a store-only ZIP of meta.json and five (seven with SH bands) lossless WebP textures;
+ * the unbundled form is the same files in a directory (index.ts:88 treats both as SOG).  The
+ * reader gives 14 + nsh float32 columns in the other readers' order: x y z scale_0..2 f_dc_0..2
+ * opacity rot_0..3 f_rest_0..nsh-1 (nsh = 0, 9, 24 or 45).
+ *
+ * The decode rules are this project's own: the exact inverses of the writer's quantisers
+ * (write-sog.ts:162-268, :319-348) in JS-number (f64) arithmetic, one Float32Array store per
+ * value, Math.exp / Math.log as V8 has them.  Texel i (row-major in the width x height textures)
+ * is splat i, bytes R G B A:
+ *   x y z      q = means_l[a] | means_u[a] << 8;  v = mins[a] + (maxs[a] - mins[a]) * (q / 65535);
+ *              out = Math.sign(v) * (Math.exp(Math.abs(v)) - 1)   (NaN / Inf in mins / maxs propagate)
+ *   rot_0..3   t = quats.A & 3 (the writer stores 252 + maxComp; any other alpha byte is read the
+ *              same way); c_k = (byte_k / 255 - 0.5) * Math.sqrt(2) for k = R, G, B;
+ *              rot_t = Math.sqrt(Math.max(0, 1 - (c0*c0 + c1*c1 + c2*c2))), the other three in
+ *              ascending index take c0, c1, c2; no renormalisation
+ *   scale_k    scales_codebook[scales.k];  f_dc_k = sh0_codebook[sh0.k]   (float32 copies)
+ *   opacity    p = sh0.A / 255;  e = Math.min(1 - 1e-6, Math.max(1e-6, p));  Math.log(e / (1 - e))
+ *   f_rest_{j + ch * C}  (C = 3 / 8 / 15 coefficients of bands 1 / 2 / 3, ch = 0..2)
+ *              label = shN_labels.R | shN_labels.G << 8; the texel at row label >> 6, column
+ *              (label & 63) * C + j of shN_centroids (width 64 * C) gives shn_codebook[texel[ch]].
+ *              A label >= palette_size writes zeros for its row and is counted.
+ *
+ * st_zip_index (host only): the entries of a ZIP archive in memory, from its central directory:
+ * name (name_len bytes at data + name_offset, not NUL-terminated), CRC-32, and where the entry's
+ * `size` bytes lie (data + offset).  entries may be NULL to query *count; cap < *count is
+ * ST_ERR_ARG.  Stored entries only: a compressed entry or a zip64 archive is ST_ERR_UNSUPPORTED;
+ * a malformed archive is ST_ERR_ARG.  Every offset and length is checked against len first.
+ * st_webp_info / st_webp_decode_lossless (host only): a WebP-lossless file (RIFF container with
+ * a VP8L chunk, alone or in a VP8X file; all of RFC 9649) -> its size / its pixels as RGBA8 rows
+ * of `stride` bytes (>= 4 * width).  A lossy file is ST_ERR_UNSUPPORTED, a truncated or corrupt
+ * one ST_ERR_ARG; nothing is read past len.
+ * st_sog_read_layout (host only, no context): the only gate before a launch.  tex_wh: the
+ * (width, height) of means_l, means_u, quats, scales, sh0, shN_centroids, shN_labels (the last
+ * two ignored for bands 0).  Checks count >= 1; the per-splat textures all width x height with
+ * width * height >= count (meta's width / height must agree); bands in 0..3; for bands > 0,
+ * 1 <= palette_size <= 65536, the centroid texture 64 * C wide and 64 * its height >= palette_size
+ * (meta's shn_width / shn_height must agree).  *n = count, *nsh = 3 * C.
+ * st_dev_sog_decode: device textures (RGBA8, 4-byte aligned) -> device columns, one kernel on the
+ * context stream; it waits for the kernel and returns ST_ERR_ARG "N shN labels outside the
+ * palette" when any label was (the columns are complete, those rows zero).  Only rows
+ * [0, count) of the columns are written.
+ * st_sog_read / st_dev_sog_read: a whole .sog in a host buffer plus the caller-parsed meta
+ * (parsing meta.json's text is the caller's job, as gunzip is for .spz; width / height /
+ * shn_width / shn_height of meta are filled from the textures here and need not be set).  The
+ * archive is indexed, the textures looked up under the writer's names (means_l.webp
+ * means_u.webp quats.webp scales.webp sh0.webp shN_centroids.webp shN_labels.webp), sized
+ * (st_webp_info), checked (st_sog_read_layout), decoded on up to 7 host threads, each uploaded as
+ * it finishes, and one kernel makes the columns (host_cols / device cols, capacity count rows). */
+typedef struct {
+    uint64_t name_offset;
+    uint32_t name_len;
+    uint32_t crc;
+    uint64_t offset;
+    uint64_t size;
+} st_zip_entry;
+int st_zip_index(const uint8_t *data, uint64_t len, st_zip_entry *entries, int32_t cap, int32_t *count);
+int st_webp_info(const uint8_t *data, uint64_t len, int32_t *width, int32_t *height);
+int st_webp_decode_lossless(const uint8_t *data, uint64_t len, uint8_t *rgba_out, int32_t stride);
+int st_sog_read_layout(const st_sog_meta *meta, uint64_t count, const int32_t tex_wh[7][2], uint64_t *n,
+                       int32_t *nsh);
+int st_dev_sog_decode(st_ctx *ctx, const st_sog_meta *meta, uint64_t count, const st_sog_textures *dev_tex,
+                      float *const *cols);
+int st_sog_read(st_ctx *ctx, const uint8_t *data, uint64_t len, const st_sog_meta *meta, uint64_t count,
+                float *const *host_cols);
+int st_dev_sog_read(st_ctx *ctx, const uint8_t *data, uint64_t len, const st_sog_meta *meta, uint64_t count,
+                    float *const *cols);
 
 #ifdef __cplusplus
 }

@@ -9,12 +9,15 @@
 //   zip_write      serialize/zip-writer.ts:35-135 (flags 0x808: CRC and sizes in a data
 //                  descriptor after the data; method 0; DOS time/date of the writer's
 //                  construction; central directory; end record without zip64)
+//   st_zip_index   the reverse, for the .sog reader: entries from the central directory
+//                  (st_zip_index.h)
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 
 #include "st_webp.h"
+#include "st_zip_index.h"
 
 namespace st {
 
@@ -222,6 +225,22 @@ int st_zip_store(const char *const *names, const uint8_t *const *data, const uin
             if (sizes[i]) std::memcpy(buf + off[i], data[i], sizes[i]);
         *out = buf;
         *out_size = total;
+    });
+}
+
+int st_zip_index(const uint8_t *data, uint64_t len, st_zip_entry *entries, int32_t cap, int32_t *count) {
+    return guard([&] {
+        ST_REQUIRE((data || !len) && count, ST_ERR_ARG, "NULL argument");
+        std::vector<st_zip_entry> es;
+        try {
+            es = zip_index(data, len);
+        } catch (const ZipIndexError &e) {
+            throw Error(e.code, e.msg);
+        }
+        *count = (int32_t)es.size();
+        if (!entries) return;
+        ST_REQUIRE(cap >= *count, ST_ERR_ARG, "zip: more entries than the caller's array holds");
+        if (!es.empty()) std::memcpy(entries, es.data(), es.size() * sizeof(st_zip_entry));
     });
 }
 

@@ -129,6 +129,8 @@ EXPORTS = [
     'st_csv_max_row_bytes', 'st_csv_header_text', 'st_dev_csv_rows', 'st_dev_csv_file', 'st_csv_file',
     'st_ply_csv_file',
     'st_base64_size', 'st_dev_base64', 'st_html_parts', 'st_html_file', 'st_ply_html_file',
+    'st_zip_index', 'st_webp_info', 'st_webp_decode_lossless', 'st_sog_read_layout', 'st_dev_sog_decode', 'st_sog_read',
+    'st_dev_sog_read',
 ]
 
 
@@ -697,6 +699,114 @@ def spz_inflate(data):
     return gzip.decompress(data)
 
 
+# ---- the .sog reader's host pieces ------------------------------------------------------------
+class ZipEntry(ctypes.Structure):
+    _fields_ = [('name_offset', ctypes.c_uint64), ('name_len', ctypes.c_uint32), ('crc', ctypes.c_uint32),
+                ('offset', ctypes.c_uint64), ('size', ctypes.c_uint64)]
+
+
+SOG_TEXTURES = ('means_l', 'means_u', 'quats', 'scales', 'sh0', 'shN_centroids', 'shN_labels')
+SOG_FILES = tuple(k + '.webp' for k in SOG_TEXTURES)
+
+
+def zip_index(data):
+    """[(name, data offset, size, crc)] of a ZIP archive's bytes from its central directory
+    (st_zip_index: stored entries only; host only)"""
+    data = bytes(data)
+    n = ctypes.c_int32(0)
+    check(lib().st_zip_index(data, ctypes.c_uint64(len(data)), None, ctypes.c_int32(0), ctypes.byref(n)))
+    es = (ZipEntry * max(n.value, 1))()
+    check(lib().st_zip_index(data, ctypes.c_uint64(len(data)), es, ctypes.c_int32(n.value), ctypes.byref(n)))
+    return [(data[e.name_offset:e.name_offset + e.name_len].decode('utf-8', 'replace'), e.offset, e.size, e.crc)
+            for e in es[:n.value]]
+
+
+def webp_info(data):
+    """(width, height) of a WebP-lossless file's bytes (host only)"""
+    data = bytes(data)
+    w, h = ctypes.c_int32(0), ctypes.c_int32(0)
+    check(lib().st_webp_info(data, ctypes.c_uint64(len(data)), ctypes.byref(w), ctypes.byref(h)))
+    return w.value, h.value
+
+
+def webp_decode_lossless(data):
+    """a WebP-lossless file's bytes -> (height, width, 4) uint8 RGBA (st_webp_decode_lossless: the
+    host VP8L decoder, all of RFC 9649)"""
+    data = bytes(data)
+    w, h = webp_info(data)
+    out = np.empty((h, w, 4), np.uint8)
+    check(lib().st_webp_decode_lossless(data, ctypes.c_uint64(len(data)), _vp(out), ctypes.c_int32(w * 4)))
+    return out
+
+
+def sog_read_meta(text):
+    """meta.json of a SOG (write-sog.ts:271-293, :350-361) -> (SogMeta, count, the texture file names
+    in SOG_TEXTURES order: five without an shN entry).  version must be 2 and every `files` entry
+    present; a JSON null (the writer's text of a non-finite number) reads as NaN.  The texture
+    sizes (width, height, shn_width, shn_height) are left 0: the textures tell them."""
+    import json
+    if isinstance(text, (bytes, bytearray)):
+        text = bytes(text).decode('utf-8')
+
+    def bad(msg):
+        return StError(ST_ERR_ARG, 'sog meta.json: ' + msg)
+
+    try:
+        m = json.loads(text)
+    except ValueError as e:
+        raise bad(str(e))
+    if not isinstance(m, dict):
+        raise bad('not an object')
+    if m.get('version') != 2:
+        raise StError(ST_ERR_UNSUPPORTED, f"sog meta.json: version {m.get('version')!r} (2 is supported)")
+    count = m.get('count')
+    if not isinstance(count, int) or isinstance(count, bool) or count < 1:
+        raise bad('count must be a positive integer')
+
+    def num(v):
+        if v is None:
+            return float('nan')
+        if isinstance(v, bool) or not isinstance(v, (int, float)):
+            raise bad('a number expected')
+        return float(v)
+
+    def files(key, n):
+        f = m.get(key, {}).get('files') if isinstance(m.get(key), dict) else None
+        if not isinstance(f, list) or len(f) != n or not all(isinstance(x, str) for x in f):
+            raise bad(f'{key}.files must list {n} file name' + ('s' if n > 1 else ''))
+        return f
+
+    def codebook(key):
+        cb = m[key].get('codebook')
+        if not isinstance(cb, list) or len(cb) != 256:
+            raise bad(f'{key}.codebook must hold 256 numbers')
+        return np.array([num(v) for v in cb], np.float64).astype(np.float32)
+
+    names = files('means', 2) + files('quats', 1) + files('scales', 1) + files('sh0', 1)
+    meta = SogMeta()
+    for key, dst in (('mins', meta.means_min), ('maxs', meta.means_max)):
+        v = m['means'].get(key)
+        if not isinstance(v, list) or len(v) != 3:
+            raise bad(f'means.{key} must hold 3 numbers')
+        for a in range(3):
+            dst[a] = num(v[a])
+    meta.scales_codebook[:] = codebook('scales').tolist()
+    meta.sh0_codebook[:] = codebook('sh0').tolist()
+    if 'shN' in m:
+        names += files('shN', 2)
+        sn = m['shN']
+        for key in ('count', 'bands'):
+            if not isinstance(sn.get(key), int) or isinstance(sn.get(key), bool):
+                raise bad(f'shN.{key} must be an integer')
+        if not 1 <= sn['bands'] <= 3:
+            raise bad('shN.bands must be 1..3')
+        if not 1 <= sn['count'] <= 65536:
+            raise bad('shN.count must be 1..65536')
+        meta.sh_bands, meta.palette_size = sn['bands'], sn['count']
+        meta.shn_codebook[:] = codebook('shN').tolist()
+    return meta, count, names
+
+
 def rccl_info():
     """(version, path) of the RCCL the library's collectives run on (st_rccl_info: loaded by path,
     /opt/rocm/lib/librccl.so.1 unless ST_RCCL says otherwise; no GPU needed)"""
@@ -1131,11 +1241,93 @@ class Context:
             data = spz_inflate(f.read())
         return self._read_bytes(data, spz_layout, lib().st_spz_read, lib().st_dev_spz_read, device)
 
+    # ---- the .sog reader (beyond the reference's CLI, which cannot read SOG) --------------------
+    def dev_sog_decode(self, meta, count, tex, out):
+        """SOG textures already in HBM (dict as dev_sog's: uint8 tensors of width * height * 4 bytes;
+        meta's width / height / shn_width / shn_height set) -> `out`, float32 tensors under
+        reader_columns(nsh).  Rows past count are not written.  StError(ST_ERR_ARG) "N shN labels
+        outside the palette" when any label was (those rows are zero)."""
+        t = SogTextures(*[(tex[k].data_ptr() if k in tex else None) for k in SOG_TEXTURES])
+        nsh = [0, 9, 24, 45][meta.sh_bands] if 0 <= meta.sh_bands <= 3 else 0
+        check(lib().st_dev_sog_decode(self.h, ctypes.byref(meta), ctypes.c_uint64(count), ctypes.byref(t),
+                                      self._col_ptrs(out, nsh)))
+
+    def _read_sog_parts(self, meta, count, images, device):
+        """decoded textures (numpy (h, w, 4), SOG_TEXTURES order) -> columns through dev_sog_decode"""
+        import torch
+        dev = 'cuda' if device is None else device
+        meta.height, meta.width = images[0].shape[:2]
+        if len(images) == 7:
+            meta.shn_height, meta.shn_width = images[5].shape[:2]
+        wh = (ctypes.c_int32 * 2 * 7)()
+        for k, im in enumerate(images):
+            wh[k][0], wh[k][1] = im.shape[1], im.shape[0]
+        n, nsh = _layout(lib().st_sog_read_layout, ctypes.byref(meta), ctypes.c_uint64(count), wh)
+        tex = {k: torch.from_numpy(np.ascontiguousarray(im).reshape(-1)).to(dev) for k, im in zip(SOG_TEXTURES, images)}
+        out = {k: torch.empty(n, dtype=torch.float32, device=dev) for k in reader_columns(nsh)}
+        self.dev_sog_decode(meta, count, tex, out)
+        return out if device is not None else {k: v.cpu().numpy() for k, v in out.items()}
+
+    def _read_sog(self, path, device):
+        from concurrent.futures import ThreadPoolExecutor
+        low = str(path).lower()
+        if low.endswith('meta.json'):
+            # the unbundled form: the textures are the sibling files meta.json names
+            with open(path, 'rb') as f:
+                meta, count, names = sog_read_meta(f.read())
+            blobs = []
+            for nm in names:
+                with open(os.path.join(os.path.dirname(os.path.abspath(path)), nm), 'rb') as f:
+                    blobs.append(f.read())
+        else:
+            with open(path, 'rb') as f:
+                data = f.read()
+            index = {}
+            for name, off, size, _ in zip_index(data):
+                index.setdefault(name, (off, size))  # the first entry of a name
+            if 'meta.json' not in index:
+                raise StError(ST_ERR_ARG, 'sog: the archive has no meta.json')
+            off, size = index['meta.json']
+            meta, count, names = sog_read_meta(data[off:off + size])
+            if tuple(names) == SOG_FILES[:len(names)]:
+                # the writer's names: the whole read in one native call
+                nsh = [0, 9, 24, 45][meta.sh_bands]
+                if names[0] in index:  # before the columns are allocated by meta.json's word alone
+                    off, size = index[names[0]]
+                    w, h = webp_info(data[off:off + size])
+                    if count > w * h:
+                        raise StError(ST_ERR_ARG, 'sog: the textures hold fewer texels than count')
+                cols, ptrs = self._reader_out(count, nsh, device)
+                read = lib().st_sog_read if device is None else lib().st_dev_sog_read
+                check(read(self.h, data, ctypes.c_uint64(len(data)), ctypes.byref(meta), ctypes.c_uint64(count), ptrs))
+                return cols
+            blobs = []
+            for nm in names:
+                if nm not in index:
+                    raise StError(ST_ERR_ARG, f'sog: the archive has no {nm}')
+                off, size = index[nm]
+                blobs.append(data[off:off + size])
+        with ThreadPoolExecutor(max_workers=len(blobs)) as pool:  # at most seven; ctypes drops the GIL
+            images = list(pool.map(webp_decode_lossless, blobs))
+        return self._read_sog_parts(meta, count, images, device)
+
+    def read_sog(self, path):
+        """a SOG -> {name: float32 numpy column} under reader_columns(nsh): `*.sog` is the bundle,
+        a path ending `meta.json` the unbundled form (index.ts:88 treats both as SOG).  Beyond the
+        reference's CLI, which writes SOG and cannot read it: the decode rules are in st_abi.h."""
+        return self._read_sog(path, None)
+
+    def read_sog_dev(self, path, device='cuda'):
+        """read_sog into device columns (torch tensors)"""
+        return self._read_sog(path, device)
+
     def read_table(self, path):
         """the CLI's input dispatch (index.ts:52-76) on the lower-cased file name: .ksplat, .splat,
-        .ply (decompressed when it is a compressed PLY, as decompress-ply.ts:35-80 tells), .spz ->
-        {name: numpy column} of the splat table"""
+        .ply (decompressed when it is a compressed PLY, as decompress-ply.ts:35-80 tells), .spz; and,
+        beyond the reference, .sog and meta.json (read_sog) -> {name: numpy column} of the splat table"""
         low = str(path).lower()
+        if low.endswith('.sog') or low.endswith('meta.json'):
+            return self.read_sog(path)
         if low.endswith('.ksplat'):
             return self.read_ksplat(path)
         if low.endswith('.splat'):
