@@ -65,6 +65,11 @@
  *   st_dev_csv_rows / st_dev_csv_file /     writeCsv (header line, rows of
  *   st_csv_file / st_ply_csv_file             Number::toString cells)            writers/write-csv.ts:5-23,
  *                                                                               index.ts:117-118
+ *   st_dev_splat_rows / st_dev_splat_file / (none: the reference reads .splat and .spz and writes
+ *     st_splat_file / st_ply_splat_file /     neither) each field the code its reader decodes to
+ *     st_spz_image_size / st_dev_spz_planes   the nearest value; rules in "the .splat and .spz
+ *     / st_dev_spz_image / st_dev_spz_file /  writers" below             readers/read-splat.ts:71-138,
+ *     st_spz_file / st_ply_spz_file                                      readers/read-spz.ts:139-232
  *
  * Conventions
  *  - Columns are SoA float32 arrays of n rows (the reference's Float32Array
@@ -825,6 +830,89 @@ int st_sog_read(st_ctx *ctx, const uint8_t *data, uint64_t len, const st_sog_met
                 float *const *host_cols);
 int st_dev_sog_read(st_ctx *ctx, const uint8_t *data, uint64_t len, const st_sog_meta *meta, uint64_t count,
                     float *const *cols);
+
+/* ---- the .splat and .spz writers (no reference counterpart: the reference reads both formats,
+ * readers/read-splat.ts and readers/read-spz.ts, and writes neither) ---------------------------
+ * The encode rules are this project's own, anchored on the reference: each field gets the code
+ * that the reference's own reader decodes to the nearest value, so writing the columns the
+ * reference decoded from a file gives the file's bytes back (tests/golden/readers.*; where a
+ * decode loses information -- a signalling NaN, a float32 scale through log, a rotation whose
+ * stored part exceeds unit length -- it cannot).
+ *
+ * v is the column's element as a JS number (float32 / float64 widened exactly, integers taken
+ * exactly; any of the eight column types).  All arithmetic is IEEE double, one rounding per
+ * operation in the order written, no fused multiply-add.  exp is V8's Math.exp;
+ * sigmoid(v) = 1 / (1 + exp(-v)).
+ *   Q8(t)  = 0 if t is NaN, else min(255, max(0, floor(t + 0.5)))
+ *   u      the unit quaternion: L = sqrt(((r0*r0 + r1*r1) + r2*r2) + r3*r3) with r_k = rot_k;
+ *          u_k = r_k / L if L > 0 and L < Infinity, else u = (1, 0, 0, 0)
+ * Required columns: x y z scale_0..2 f_dc_0..2 opacity rot_0..3.  A missing one is ST_ERR_ARG and
+ * the message names it; the first column of a name wins; other columns (nx, ...) are ignored.
+ * The band C (0, 3, 8 or 15 coefficients per channel) follows the first-missing-f_rest_i rule
+ * (transform.ts:20).  Columns must be aligned to their type.
+ *
+ * .splat: 32 bytes per row, little endian, in row order (no importance sort: a caller who wants
+ * one permutes first).  f_rest columns are ignored.  n = 0 is ST_ERR_ARG (the reference's reader
+ * refuses an empty file).
+ *   bytes  0-11  x, y, z as float32: a float32 column's bits unchanged (NaN payloads included),
+ *                other types Math.fround(v)
+ *         12-23  Math.fround(exp(scale_k))
+ *         24-26  Q8((f_dc_k * 0.28209479177387814 + 0.5) * 255)
+ *         27     Q8(sigmoid(opacity) * 255)
+ *         28-31  Q8((u_k + 1) * 127.5), k = 0..3
+ *
+ * .spz: version 2 only.  The raw image (what the reference's reader takes after its gunzip) is a
+ * 16-byte header and six planes, 16 + n * (19 + 3C) bytes:
+ *   header  0-3 4E 47 53 50;  4-7 u32 2;  8-11 u32 n;  12 degree 0..3;  13 fractional_bits;  14-15 0
+ *   positions  9 B per splat: x, y, z as the little-endian low 24 bits of k;  k = 0 if v is NaN,
+ *              else min(2^23 - 1, max(-2^23, floor(v * 2^fractional_bits + 0.5)))
+ *   alphas     Q8(sigmoid(opacity) * 255)
+ *   colours    Q8((f_dc_k * 0.15 + 0.5) * 255)
+ *   scales     Q8((scale_k + 10) * 16)
+ *   rotations  u as above; if u_0 < 0 all four are negated; then Q8((u_k + 1) * 127.5), k = 1, 2, 3
+ *   harmonics  for i = 0..3C-1: Q8(f_rest_{(i mod 3) * C + floor(i / 3)} * 128 + 128)
+ * fractional_bits is 0..23 (outside: ST_ERR_ARG).  *out_clamped (nullable) counts the position
+ * values that were NaN or fell outside [-2^23, 2^23 - 1] before the clamp -- whether or not the
+ * positions plane is asked for; the caller decides whether to retry with fewer bits.
+ * n >= 2^32 is ST_ERR_UNSUPPORTED; n = 0 writes the header alone.
+ *
+ * st_spz_image_size (host only): 16 + n * (19 + 3 * sh_coeffs); 0 for an sh_coeffs that is no
+ * band or n >= 2^32.
+ * st_dev_splat_rows: rows [row0, row0 + nrows) of a device table as nrows x 32 bytes at dev_rows
+ * (device, 4-byte aligned), queued on the context stream.
+ * st_dev_spz_planes: the same rows' bytes of each plane at planes[0..5] (positions, alphas,
+ * colours, scales, rotations, harmonics; device, ANY alignment: where row0's bytes of that plane
+ * go; NULL skips one).  Waits for the kernel (the count).
+ * st_dev_spz_image: header + planes of the whole table at dev_out (device, any alignment).
+ * *size = the bytes the image needs; above cap the call returns ST_ERR_ARG and writes nothing.
+ * No byte outside the stated output ranges is ever written by any of them.
+ * The file forms follow st_dev_csv_file / st_csv_file / st_ply_csv_file: processDataTable through
+ * the same chain, out_fd seekable, open for writing and not O_APPEND (ST_ERR_ARG before any
+ * work), written from its position, which ends after the output; a longer file is cut there;
+ * *out_m = the row count, *size = the bytes written; one device (the st_set_devices group is not
+ * consulted).  The .splat rows are encoded a pinned slot at a time and never exist in HBM at
+ * once; the .spz forms write the RAW image, built whole in HBM: what readSpz decodes after its
+ * gunzip (st_spz_layout / st_spz_read take it as is).  The gzip member around it, which readSpz
+ * itself (read-spz.ts:56-75 stops on a file without the gzip magic) and other .spz consumers
+ * expect, is the caller's, as gunzip is for the reader. */
+uint64_t st_spz_image_size(uint64_t n, int32_t sh_coeffs);
+int st_dev_splat_rows(st_ctx *ctx, const st_ttable *dev_table, uint64_t row0, uint64_t nrows, uint8_t *dev_rows);
+int st_dev_spz_planes(st_ctx *ctx, const st_ttable *dev_table, int32_t fractional_bits, uint64_t row0,
+                      uint64_t nrows, uint8_t *const planes[6], uint64_t *out_clamped);
+int st_dev_spz_image(st_ctx *ctx, const st_ttable *dev_table, int32_t fractional_bits, uint8_t *dev_out,
+                     uint64_t cap, uint64_t *size, uint64_t *out_clamped);
+int st_dev_splat_file(st_ctx *ctx, const st_ttable *dev_table, int32_t out_fd, uint64_t *size);
+int st_splat_file(st_ctx *ctx, const st_ttable *src, const st_action *actions, int32_t nactions, int32_t out_fd,
+                  uint64_t *out_m, uint64_t *size);
+int st_ply_splat_file(st_ctx *ctx, int32_t fd, const st_ply_header *h, int32_t element, const st_action *actions,
+                      int32_t nactions, int32_t out_fd, uint64_t *out_m, uint64_t *size);
+int st_dev_spz_file(st_ctx *ctx, const st_ttable *dev_table, int32_t fractional_bits, int32_t out_fd,
+                    uint64_t *size, uint64_t *out_clamped);
+int st_spz_file(st_ctx *ctx, const st_ttable *src, const st_action *actions, int32_t nactions,
+                int32_t fractional_bits, int32_t out_fd, uint64_t *out_m, uint64_t *size, uint64_t *out_clamped);
+int st_ply_spz_file(st_ctx *ctx, int32_t fd, const st_ply_header *h, int32_t element, const st_action *actions,
+                    int32_t nactions, int32_t fractional_bits, int32_t out_fd, uint64_t *out_m, uint64_t *size,
+                    uint64_t *out_clamped);
 
 #ifdef __cplusplus
 }

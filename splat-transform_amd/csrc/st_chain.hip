@@ -559,6 +559,64 @@ uint64_t csv_table_to_file(st_ctx *c, const st_ttable *t, int fd) {
     return total - base;
 }
 
+// the .splat rows of a device table to fd from its position: pieces of one ring slot of 32-byte
+// rows are encoded into two device staging buffers and come down through the ring -- the n x 32
+// bytes never exist in HBM at once.  The table's own errors come before the first byte is written
+uint64_t splat_table_to_file(st_ctx *c, const st_ttable *t, int fd) {
+    const WrTable W = wr_table(t, false, "splat file");
+    ST_REQUIRE(W.n != 0, ST_ERR_ARG, "splat file: a .splat file of no rows is one the reader refuses");
+    const uint64_t base = file_base(fd, "splat file");
+    {
+        FileRing ring(c, fd);
+        const uint64_t piece_rows = std::max<uint64_t>(1, ring.slot / 32);
+        uint8_t *stage[2] = {wsT<uint8_t>(c, "splatw.stage0", piece_rows * 32), wsT<uint8_t>(c, "splatw.stage1", piece_rows * 32)};
+        try {
+            int k = 0;
+            for (uint64_t row = 0; row < W.n; row += piece_rows, ++k) {
+                const uint64_t nr = std::min(piece_rows, W.n - row), nb = nr * 32;
+                uint8_t *host = ring.next();
+                if (!host) break;
+                splat_rows_dev(c, W, row, nr, stage[k & 1]);
+                ST_HIP(hipMemcpyAsync(host, stage[k & 1], nb, hipMemcpyDeviceToHost, c->stream));
+                ring.submit(nb, base + row * 32);
+            }
+        } catch (...) {
+            ring.fail(std::current_exception());
+        }
+        ring.finish();
+    }
+    file_end(fd, base + W.n * 32, "splat file");
+    return W.n * 32;
+}
+
+// the raw .spz image (header + six planes) of a device table to fd from its position: built whole
+// in HBM -- it is smaller than the table it comes from -- and copied down through the ring
+uint64_t spz_table_to_file(st_ctx *c, const st_ttable *t, int fractional_bits, int fd, uint64_t *clamped) {
+    const WrTable W = wr_table(t, true, "spz file");
+    spz_check(W, fractional_bits);
+    const uint64_t base = file_base(fd, "spz file");
+    const uint64_t size = spz_image_size(W.n, W.C);
+    auto *image = wsT<uint8_t>(c, "spzw.image", size);
+    spz_image_dev(c, W, fractional_bits, image, clamped);
+    {
+        FileRing ring(c, fd);
+        try {
+            for (uint64_t o = 0; o < size; o += ring.slot) {
+                const uint64_t nb = std::min(ring.slot, size - o);
+                uint8_t *host = ring.next();
+                if (!host) break;
+                ST_HIP(hipMemcpyAsync(host, image + o, nb, hipMemcpyDeviceToHost, c->stream));
+                ring.submit(nb, base + o);
+            }
+        } catch (...) {
+            ring.fail(std::current_exception());
+        }
+        ring.finish();
+    }
+    file_end(fd, base + size, "spz file");
+    return size;
+}
+
 // the host table into the chain
 auto host_loader(st_ctx *c, const st_ttable *src) {
     return [=](Chain &ch) {
@@ -917,6 +975,89 @@ int st_ply_csv_file(st_ctx *c, int32_t fd, const st_ply_header *h, int32_t eleme
         ply_chain(c, fd, h, element, ch);
         run_actions(ch, actions, nactions);
         *size = csv_table_to_file(c, ch.typed(), out_fd);
+        *out_m = ch.n;
+    });
+}
+
+int st_dev_splat_file(st_ctx *c, const st_ttable *t, int32_t out_fd, uint64_t *size) {
+    return guard([&] {
+        ST_REQUIRE(c && t && size, ST_ERR_ARG, "NULL argument");
+        check_src(t);
+        sog_file_check(out_fd);
+        use_device(c);
+        *size = splat_table_to_file(c, t, out_fd);
+    });
+}
+
+int st_splat_file(st_ctx *c, const st_ttable *src, const st_action *actions, int32_t nactions, int32_t out_fd,
+                  uint64_t *out_m, uint64_t *size) {
+    return guard([&] {
+        ST_REQUIRE(c && src && out_m && size && (actions || nactions == 0), ST_ERR_ARG, "NULL argument");
+        check_src(src);
+        sog_file_check(out_fd);
+        use_device(c);
+        Chain ch{c};
+        upload_chain(c, src, ch);
+        run_actions(ch, actions, nactions);
+        *size = splat_table_to_file(c, ch.typed(), out_fd);
+        *out_m = ch.n;
+    });
+}
+
+int st_ply_splat_file(st_ctx *c, int32_t fd, const st_ply_header *h, int32_t element, const st_action *actions,
+                      int32_t nactions, int32_t out_fd, uint64_t *out_m, uint64_t *size) {
+    return guard([&] {
+        ST_REQUIRE(c && h && fd >= 0 && out_m && size && (actions || nactions == 0), ST_ERR_ARG, "NULL argument");
+        sog_file_check(out_fd);
+        use_device(c);
+        Chain ch{c};
+        ply_chain(c, fd, h, element, ch);
+        run_actions(ch, actions, nactions);
+        *size = splat_table_to_file(c, ch.typed(), out_fd);
+        *out_m = ch.n;
+    });
+}
+
+int st_dev_spz_file(st_ctx *c, const st_ttable *t, int32_t fractional_bits, int32_t out_fd, uint64_t *size,
+                    uint64_t *out_clamped) {
+    return guard([&] {
+        ST_REQUIRE(c && t && size, ST_ERR_ARG, "NULL argument");
+        ST_REQUIRE(fractional_bits >= 0 && fractional_bits <= 23, ST_ERR_ARG, "spz: fractional_bits must be 0..23");
+        check_src(t);
+        sog_file_check(out_fd);
+        use_device(c);
+        *size = spz_table_to_file(c, t, fractional_bits, out_fd, out_clamped);
+    });
+}
+
+int st_spz_file(st_ctx *c, const st_ttable *src, const st_action *actions, int32_t nactions, int32_t fractional_bits,
+                int32_t out_fd, uint64_t *out_m, uint64_t *size, uint64_t *out_clamped) {
+    return guard([&] {
+        ST_REQUIRE(c && src && out_m && size && (actions || nactions == 0), ST_ERR_ARG, "NULL argument");
+        ST_REQUIRE(fractional_bits >= 0 && fractional_bits <= 23, ST_ERR_ARG, "spz: fractional_bits must be 0..23");
+        check_src(src);
+        sog_file_check(out_fd);
+        use_device(c);
+        Chain ch{c};
+        upload_chain(c, src, ch);
+        run_actions(ch, actions, nactions);
+        *size = spz_table_to_file(c, ch.typed(), fractional_bits, out_fd, out_clamped);
+        *out_m = ch.n;
+    });
+}
+
+int st_ply_spz_file(st_ctx *c, int32_t fd, const st_ply_header *h, int32_t element, const st_action *actions,
+                    int32_t nactions, int32_t fractional_bits, int32_t out_fd, uint64_t *out_m, uint64_t *size,
+                    uint64_t *out_clamped) {
+    return guard([&] {
+        ST_REQUIRE(c && h && fd >= 0 && out_m && size && (actions || nactions == 0), ST_ERR_ARG, "NULL argument");
+        ST_REQUIRE(fractional_bits >= 0 && fractional_bits <= 23, ST_ERR_ARG, "spz: fractional_bits must be 0..23");
+        sog_file_check(out_fd);
+        use_device(c);
+        Chain ch{c};
+        ply_chain(c, fd, h, element, ch);
+        run_actions(ch, actions, nactions);
+        *size = spz_table_to_file(c, ch.typed(), fractional_bits, out_fd, out_clamped);
         *out_m = ch.n;
     });
 }

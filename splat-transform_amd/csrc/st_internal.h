@@ -450,6 +450,32 @@ std::string csv_header_text(const st_ttable *t);  // write-csv.ts:9-10
 // st_numfmt.h's power-of-ten table on the host (built at first use): 2 * POW10_ENTRIES words
 const uint64_t *numfmt_host_table();
 
+// the .splat and .spz writers (st_writers.hip; the rules: st_abi.h, "the .splat and .spz writers").
+// wr_table picks the fourteen required columns by name (the first of a name wins; a missing one,
+// a bad type or a misaligned column is ST_ERR_ARG under `what`) and, with_sh, the 3C f_rest
+// columns of the table's band.  Slots: x y z scale_0..2 f_dc_0..2 opacity rot_0..3 f_rest_0..
+struct WrCol {
+    const void *p;
+    int32_t t, pad;
+};
+struct WrCols {
+    WrCol c[14 + 45];
+};
+struct WrTable {
+    WrCols cols;
+    uint64_t n;
+    int C;     // SH coefficients per channel: 0 without with_sh
+    bool f32;  // every picked column is float32
+};
+WrTable wr_table(const st_ttable *t, bool with_sh, const char *what);
+// rows [row0, row0 + nrows) as nrows x 32 bytes at out (device, 4-byte aligned), queued on the stream
+void splat_rows_dev(st_ctx *c, const WrTable &W, uint64_t row0, uint64_t nrows, uint8_t *out);
+uint64_t spz_image_size(uint64_t n, int C);  // 0 for a C that is no band or n >= 2^32
+void spz_check(const WrTable &W, int fractional_bits);  // ST_ERR_ARG / ST_ERR_UNSUPPORTED of the rules
+// header + six planes of the whole table at out (device, any alignment, spz_image_size bytes);
+// waits for the stream; *clamped (nullable) = the position values clamped.  Returns the size
+uint64_t spz_image_dev(st_ctx *c, const WrTable &W, int fractional_bits, uint8_t *out, uint64_t *clamped);
+
 // the HTML viewer writer (write-html.ts, st_html.hip).  base64_dev queues k_base64 on the context
 // stream: the RFC 4648 text of bytes [byte0, byte0 + nbytes) of the stream that up to B64_MAX_SEGS
 // device segments make back to back, contiguous at out (device, 4-byte aligned).  base64_check

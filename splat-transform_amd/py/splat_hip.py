@@ -131,6 +131,8 @@ EXPORTS = [
     'st_base64_size', 'st_dev_base64', 'st_html_parts', 'st_html_file', 'st_ply_html_file',
     'st_zip_index', 'st_webp_info', 'st_webp_decode_lossless', 'st_sog_read_layout', 'st_dev_sog_decode', 'st_sog_read',
     'st_dev_sog_read',
+    'st_spz_image_size', 'st_dev_splat_rows', 'st_dev_spz_planes', 'st_dev_spz_image', 'st_dev_splat_file',
+    'st_splat_file', 'st_ply_splat_file', 'st_dev_spz_file', 'st_spz_file', 'st_ply_spz_file',
 ]
 
 
@@ -166,10 +168,12 @@ def lib():
         L.st_csv_max_row_bytes.restype = ctypes.c_uint64
         L.st_base64_size.restype = ctypes.c_uint64
         L.st_base64_size.argtypes = [ctypes.c_uint64]
+        L.st_spz_image_size.restype = ctypes.c_uint64
+        L.st_spz_image_size.argtypes = [ctypes.c_uint64, ctypes.c_int32]
         for name in EXPORTS:
             if name not in ('st_last_error', 'st_ctx_last_timings', 'st_ctx_last_kmeans_stats', 'st_ctx_destroy', 'st_free', 'st_webp_max_size',
                             'st_ply_row_bytes', 'st_csv_max_row_bytes', 'st_base64_size', 'st_comm_destroy',
-                            'st_group_destroy'):
+                            'st_group_destroy', 'st_spz_image_size'):
                 getattr(L, name).restype = ctypes.c_int
         _lib = L
     return _lib
@@ -697,6 +701,44 @@ def spz_inflate(data):
         raise StError(ST_ERR_ARG, 'File too small to be valid .spz format')
     import gzip
     return gzip.decompress(data)
+
+
+def spz_image_size(n, sh_coeffs):
+    """the bytes of a raw .spz image of n splats with sh_coeffs (0, 3, 8 or 15) coefficients per
+    channel: 16 + n * (19 + 3 * sh_coeffs); 0 for a bad argument (st_spz_image_size; host only)"""
+    return lib().st_spz_image_size(ctypes.c_uint64(n), ctypes.c_int32(sh_coeffs))
+
+
+SPZ_DEFLATE_SEGMENT = 8 << 20
+
+
+def spz_deflate(raw, level, threads=8, _segment=SPZ_DEFLATE_SEGMENT):
+    """ONE gzip member (mtime 0, no name) whose inflation is `raw`: the form .spz consumers expect
+    around the raw image.  Fixed segments of 8 MiB are raw-deflated independently on up to
+    min(threads, 8) threads (zlib releases the GIL), every segment but the last ended with a sync
+    flush -- a byte boundary, so the pieces concatenate into one deflate stream -- and the last with
+    finish; one CRC-32 runs over the whole input.  The bytes do not depend on the thread count."""
+    import zlib
+    from concurrent.futures import ThreadPoolExecutor
+    raw = memoryview(raw).cast('B')
+    segs = [raw[o:o + _segment] for o in range(0, len(raw), _segment)] or [raw[:0]]
+
+    def deflate(i):
+        c = zlib.compressobj(level, zlib.DEFLATED, -15)
+        return c.compress(segs[i]) + c.flush(zlib.Z_FINISH if i + 1 == len(segs) else zlib.Z_SYNC_FLUSH)
+
+    nthreads = max(1, min(int(threads), 8, len(segs)))
+    if nthreads == 1:
+        parts = [deflate(i) for i in range(len(segs))]
+    else:
+        with ThreadPoolExecutor(nthreads) as pool:
+            parts = list(pool.map(deflate, range(len(segs))))
+    crc = 0
+    for s in segs:
+        crc = zlib.crc32(s, crc)
+    # ID1 ID2 CM=8 FLG=0 MTIME=0 XFL=0 OS=255 (unknown)
+    head = b'\x1f\x8b\x08\x00\x00\x00\x00\x00\x00\xff'
+    return head + b''.join(parts) + (crc & 0xffffffff).to_bytes(4, 'little') + (len(raw) & 0xffffffff).to_bytes(4, 'little')
 
 
 # ---- the .sog reader's host pieces ------------------------------------------------------------
@@ -1655,6 +1697,162 @@ class Context:
         finally:
             os.close(fd)
         return m.value, size.value
+
+    # ---- the .splat and .spz writers (st_abi.h, "the .splat and .spz writers") ------------------
+    def dev_splat_rows(self, cols, out, row0=0, nrows=None):
+        """st_dev_splat_rows: rows [row0, row0 + nrows) of device columns (list of (name, tensor) or a
+        dict, any types) as 32-byte .splat rows at `out`, a device uint8 tensor (4-byte aligned) of
+        >= nrows * 32 bytes"""
+        t = make_ttable(cols)
+        if nrows is None:
+            nrows = t.n - row0
+        if out.numel() < 32 * nrows:
+            raise StError(ST_ERR_ARG, 'splat rows: the output buffer is too small')
+        check(lib().st_dev_splat_rows(self.h, ctypes.byref(t), ctypes.c_uint64(row0), ctypes.c_uint64(nrows), _ptr(out)))
+
+    def dev_spz_planes(self, cols, planes, fractional_bits=12, row0=0, nrows=None):
+        """st_dev_spz_planes: rows [row0, row0 + nrows) of device columns into the six .spz planes
+        (positions, alphas, colours, scales, rotations, harmonics): `planes` is a list of six device
+        uint8 tensors of any alignment -- where row0's bytes of each plane go -- or None to skip one
+        -> the position values clamped"""
+        t = make_ttable(cols)
+        if nrows is None:
+            nrows = t.n - row0
+        ptrs = (ctypes.c_void_p * 6)(*[(p.data_ptr() if p is not None else None) for p in planes])
+        clamped = ctypes.c_uint64()
+        check(lib().st_dev_spz_planes(self.h, ctypes.byref(t), ctypes.c_int32(fractional_bits), ctypes.c_uint64(row0),
+                                      ctypes.c_uint64(nrows), ptrs, ctypes.byref(clamped)))
+        return clamped.value
+
+    def dev_spz_image(self, cols, out, fractional_bits=12):
+        """st_dev_spz_image: the raw .spz image (header + planes) of device columns at `out`, a device
+        uint8 tensor of any alignment -> (bytes written, position values clamped).  A tensor too small
+        raises ST_ERR_ARG and is left untouched"""
+        t = make_ttable(cols)
+        size, clamped = ctypes.c_uint64(), ctypes.c_uint64()
+        check(lib().st_dev_spz_image(self.h, ctypes.byref(t), ctypes.c_int32(fractional_bits), _ptr(out),
+                                     ctypes.c_uint64(out.numel()), ctypes.byref(size), ctypes.byref(clamped)))
+        return size.value, clamped.value
+
+    def dev_splat_file(self, cols, out):
+        """a table already in HBM (list of (name, tensor) or a dict) as a .splat file in `out`, a path
+        or a descriptor (written from its position) -> bytes written"""
+        t = make_ttable(cols)
+        size = ctypes.c_uint64()
+        with _OutFd(out) as fd:
+            check(lib().st_dev_splat_file(self.h, ctypes.byref(t), fd, ctypes.byref(size)))
+        return size.value
+
+    def splat_file(self, cols, actions, out):
+        """processDataTable + the .splat writer on a host table (list of (name, numpy array) or a
+        dict) into `out`, a path or a descriptor (st_splat_file): (rows written, file bytes)"""
+        items = list(cols.items()) if isinstance(cols, dict) else list(cols)
+        ts = make_ttable(items, len(items[0][1]) if items else 0)
+        acts = make_actions(actions)
+        m, size = ctypes.c_uint64(), ctypes.c_uint64()
+        with _OutFd(out) as fd:
+            check(lib().st_splat_file(self.h, ctypes.byref(ts), acts, ctypes.c_int32(len(actions)), fd,
+                                      ctypes.byref(m), ctypes.byref(size)))
+        return m.value, size.value
+
+    def ply_splat_file(self, path, actions, out, element=-1):
+        """`in.ply [actions] out.splat` (st_ply_splat_file): the element's rows stay in HBM from
+        ingest to output: (rows written, file bytes)"""
+        fd = os.open(path, os.O_RDONLY)
+        try:
+            h = PlyHeader()
+            check(lib().st_ply_read_header(ctypes.c_int32(fd), ctypes.byref(h)))
+            acts = make_actions(actions)
+            m, size = ctypes.c_uint64(), ctypes.c_uint64()
+            with _OutFd(out) as ofd:
+                check(lib().st_ply_splat_file(self.h, ctypes.c_int32(fd), ctypes.byref(h), ctypes.c_int32(element), acts,
+                                              ctypes.c_int32(len(actions)), ofd, ctypes.byref(m), ctypes.byref(size)))
+        finally:
+            os.close(fd)
+        return m.value, size.value
+
+    @staticmethod
+    def _spz_out(call, out, gzip_level):
+        """call(fd) runs a .spz file form into a descriptor and returns (rows, raw bytes, clamped).
+        gzip_level 0: straight into `out`.  Otherwise the raw image goes into an anonymous memory
+        file, spz_deflate makes the one gzip member and that is written at out's position, under the
+        library's rules for an output descriptor: (rows, file bytes, clamped)"""
+        if gzip_level == 0:
+            with _OutFd(out) as fd:
+                return call(fd)
+        import fcntl
+        import mmap
+        with _OutFd(out) as fd:
+            try:
+                flags = fcntl.fcntl(fd.value, fcntl.F_GETFL)
+                pos = os.lseek(fd.value, 0, os.SEEK_CUR)
+            except OSError:
+                raise StError(ST_ERR_ARG, 'spz file: the output descriptor is not a seekable file') from None
+            if flags & os.O_ACCMODE == os.O_RDONLY or flags & os.O_APPEND:
+                raise StError(ST_ERR_ARG, 'spz file: the output descriptor must be open for writing, not O_APPEND')
+            mfd = os.memfd_create('spz_raw')
+            try:
+                rows, size, clamped = call(ctypes.c_int32(mfd))
+                mm = mmap.mmap(mfd, size, access=mmap.ACCESS_READ)
+                try:
+                    member = spz_deflate(mm, gzip_level)
+                finally:
+                    mm.close()
+            finally:
+                os.close(mfd)
+            done = 0
+            while done < len(member):
+                done += os.pwrite(fd.value, memoryview(member)[done:done + (1 << 30)], pos + done)
+            os.ftruncate(fd.value, pos + len(member))
+            os.lseek(fd.value, pos + len(member), os.SEEK_SET)
+            return rows, len(member), clamped
+
+    def dev_spz_file(self, cols, out, fractional_bits=12, gzip_level=6):
+        """a table already in HBM (list of (name, tensor) or a dict) as a .spz file in `out`, a path or
+        a descriptor (written from its position): (rows, file bytes, position values clamped).
+        gzip_level 0 writes the raw image; otherwise one gzip member around it (spz_deflate)"""
+        t = make_ttable(cols)
+
+        def call(fd):
+            size, clamped = ctypes.c_uint64(), ctypes.c_uint64()
+            check(lib().st_dev_spz_file(self.h, ctypes.byref(t), ctypes.c_int32(fractional_bits), fd, ctypes.byref(size),
+                                        ctypes.byref(clamped)))
+            return t.n, size.value, clamped.value
+        return self._spz_out(call, out, gzip_level)
+
+    def spz_file(self, cols, actions, out, fractional_bits=12, gzip_level=6):
+        """processDataTable + the .spz writer on a host table (list of (name, numpy array) or a dict)
+        into `out` (st_spz_file): (rows written, file bytes, position values clamped)"""
+        items = list(cols.items()) if isinstance(cols, dict) else list(cols)
+        ts = make_ttable(items, len(items[0][1]) if items else 0)
+        acts = make_actions(actions)
+
+        def call(fd):
+            m, size, clamped = ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_uint64()
+            check(lib().st_spz_file(self.h, ctypes.byref(ts), acts, ctypes.c_int32(len(actions)),
+                                    ctypes.c_int32(fractional_bits), fd, ctypes.byref(m), ctypes.byref(size),
+                                    ctypes.byref(clamped)))
+            return m.value, size.value, clamped.value
+        return self._spz_out(call, out, gzip_level)
+
+    def ply_spz_file(self, path, actions, out, fractional_bits=12, gzip_level=6, element=-1):
+        """`in.ply [actions] out.spz` (st_ply_spz_file): the element's rows stay in HBM from ingest to
+        the image: (rows written, file bytes, position values clamped)"""
+        acts = make_actions(actions)
+
+        def call(ofd):
+            fd = os.open(path, os.O_RDONLY)
+            try:
+                h = PlyHeader()
+                check(lib().st_ply_read_header(ctypes.c_int32(fd), ctypes.byref(h)))
+                m, size, clamped = ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_uint64()
+                check(lib().st_ply_spz_file(self.h, ctypes.c_int32(fd), ctypes.byref(h), ctypes.c_int32(element), acts,
+                                            ctypes.c_int32(len(actions)), ctypes.c_int32(fractional_bits), ofd,
+                                            ctypes.byref(m), ctypes.byref(size), ctypes.byref(clamped)))
+            finally:
+                os.close(fd)
+            return m.value, size.value, clamped.value
+        return self._spz_out(call, out, gzip_level)
 
     # ---- writeHtml (write-html.ts) -------------------------------------------------------
     def dev_base64(self, segs, out, byte0=0, nbytes=None):
