@@ -70,6 +70,11 @@
  *     st_spz_image_size / st_dev_spz_planes   the nearest value; rules in "the .splat and .spz
  *     / st_dev_spz_image / st_dev_spz_file /  writers" below             readers/read-splat.ts:71-138,
  *     st_spz_file / st_ply_spz_file                                      readers/read-spz.ts:139-232
+ *   st_ksplat_image_size /                  (none: the reference reads .ksplat and does not write
+ *     st_dev_ksplat_plan /                    it) spatial buckets, then each field the code its
+ *     st_dev_ksplat_records /                 reader decodes to the nearest value; rules in "the
+ *     st_dev_ksplat_image / st_dev_ksplat_file  .ksplat writer" below      readers/read-ksplat.ts:103-384
+ *     / st_ksplat_file / st_ply_ksplat_file
  *
  * Conventions
  *  - Columns are SoA float32 arrays of n rows (the reference's Float32Array
@@ -913,6 +918,122 @@ int st_spz_file(st_ctx *ctx, const st_ttable *src, const st_action *actions, int
 int st_ply_spz_file(st_ctx *ctx, int32_t fd, const st_ply_header *h, int32_t element, const st_action *actions,
                     int32_t nactions, int32_t fractional_bits, int32_t out_fd, uint64_t *out_m, uint64_t *size,
                     uint64_t *out_clamped);
+
+/* ---- the .ksplat writer (no reference counterpart: the reference reads the format,
+ * readers/read-ksplat.ts:103-384, and has no writer for it) ---------------------------------------
+ * The rules are this project's own, anchored on the reference's reader as "the .splat and .spz
+ * writers" above are: each field gets the code that readKsplat decodes to the nearest value.  v,
+ * the arithmetic (IEEE double, one rounding per operation in the order written, no fused
+ * multiply-add, V8's exp), Q8(t), sigmoid, the unit quaternion u, the required columns, the band
+ * rule and the any-of-eight-column-types rule are those of that section.
+ *
+ * Parameters
+ *   mode        0, 1 or 2, the compression mode (else ST_ERR_ARG)
+ *   degree      -1..3; -1: the table's own by the band rule.  A degree below the table's drops the
+ *               higher bands with filterBands' column mapping (process.ts:110-136: coefficient j
+ *               of channel ch stays f_rest_{ch * C_table + j}); above the table's: ST_ERR_ARG
+ *   block_size  a float32 B (a caller holding a double rounds it to float32 first), finite and
+ *               > 0 (else ST_ERR_ARG); 5.0 is the usual choice
+ *   sh_min, sh_max  float32, mode 2 only: both finite and non-zero with sh_min < sh_max (else
+ *               ST_ERR_ARG: the reader substitutes -1.5 / 1.5 for a zero header field,
+ *               read-ksplat.ts:135-136, so a zero would not be read back).  Modes 0 and 1 ignore
+ *               them and write -1.5 and 1.5
+ *   n = 0 is ST_ERR_ARG (the reader refuses an empty file, :138); n >= 2^32 is ST_ERR_UNSUPPORTED
+ *
+ * Grid and buckets (all modes; ONE section; bucket capacity 256)
+ *   lo_a      the least finite v on axis a over all rows; 0 if the axis has no finite value
+ *   cell_a(v) 0 if v is NaN or v < lo_a, else min(2^21 - 1, floor((v - lo_a) / B)): +Inf lands in
+ *             the last cell
+ *   key       cell_z * 2^42 + cell_y * 2^21 + cell_x
+ *   Rows are stably sorted by key (on equal keys the lower row index first).  A cell holding m
+ *   rows gives floor(m / 256) full buckets from its first rows and, if m mod 256 != 0, one partial
+ *   bucket of the rest.  In the file all full buckets come first, in key order, rows in sorted
+ *   order inside each; then all partial buckets, in key order.  No bucket has size 0.  This is the
+ *   layout the reader's walk assumes (:251-269: it advances at most one partial bucket per splat).
+ *   The bucket centre is Math.fround(lo_a + (cell_a + 0.5) * B) per axis.
+ *   *out_clamped (nullable) counts the position values that are not finite or whose unclamped cell
+ *   is >= 2^21; the caller decides whether to write again with a larger block.
+ *
+ * File (little endian; every byte not listed is 0), F / P the full / partial bucket counts:
+ *   main header, 4096 bytes: byte 0 = 0, byte 1 = 1 (version 0.1); u32 at 4 = 1 (maxSections);
+ *     u32 at 8 = 1 and u32 at 12 = n (the reference's reader reads neither; the original format's
+ *     section count and maximum splat count are believed to sit there -- nothing available when
+ *     this was written pins them); u32 at 16 = n; u16 at 20 = mode; f32 at 36 / 40 = sh_min /
+ *     sh_max (-1.5 / 1.5 in modes 0 and 1)
+ *   section header, 1024 bytes at 4096: u32 at 0 and 4 = n; u32 at 8 = 256; u32 at 12 = F + P;
+ *     f32 at 16 = B; u16 at 20 = 12; u32 at 24 = 32767; u32 at 32 / 36 = F / P; u16 at 40 = degree
+ *   then the partial bucket sizes (u32 each), the bucket centres (3 x f32 per bucket, full buckets
+ *   then partial buckets) and the records; each of these offsets is a multiple of 4.
+ *   size = 5120 + 4 P + 12 (F + P) + n * stride; stride = 44 + 4 * 3C, 24 + 2 * 3C or 24 + 3C for
+ *   modes 0, 1, 2 (C the file's coefficients per channel)
+ *
+ * Records (the offsets of COMPRESSION_MODES, :62-99).  H(t) is IEEE round-to-nearest-even from the
+ * double to binary16: |t| >= 65520 gives +-Inf, NaN gives 0x7E00, subnormals are produced.
+ *   centre, mode 0       float32: a float32 column's bits unchanged, other types Math.fround(v)
+ *   centre, modes 1, 2   ps = B / 2 / 32767, c = the row's bucket centre widened to double,
+ *                        dec(k) = Math.fround((k - 32767) * ps + c) (the reader's decode, :278).
+ *                        f = floor((v - c) / ps + 0.5) + 32767; the code is 0 if f is NaN (v is
+ *                        NaN), else k0 = min(65535, max(0, f)) corrected by the reader's own
+ *                        decode: of k0 - 1, k0, k0 + 1 inside 0..65535 the one with the least
+ *                        |dec(k) - v|; k0 wins a tie, k0 - 1 a tie between the neighbours.  (The
+ *                        bare closed form is not always the nearest code: dec's float32 store
+ *                        moves values by up to half a float32 step of |c|, which is not small
+ *                        beside ps for buckets far from the origin.)  Stored as a u16
+ *   scale                t = exp(scale_k); mode 0 Math.fround(t), modes 1 and 2 H(t).  A t that
+ *                        rounds to 0 reads back as -10 (:321), not as scale_k
+ *   rotation             u in the order rot_0..3 the reader stores back (:296-307), no sign
+ *                        change; mode 0 Math.fround(u_k), modes 1 and 2 H(u_k)
+ *   colour, opacity      Q8((f_dc_k * 0.28209479177387814 + 0.5) * 255), Q8(sigmoid(opacity) * 255)
+ *   harmonics            file component i takes the column the reader's mapping sends it to
+ *                        (:343-362: band by band, channel-major inside a band).  Mode 0: float32 as
+ *                        for the centre; mode 1: H(v); mode 2: with lo = sh_min and span = sh_max -
+ *                        sh_min (the header's float32 values widened, the subtraction in double),
+ *                        dec(b) = Math.fround(lo + (b / 255) * span) (:242-243); the byte is 0 if v
+ *                        is NaN, else k0 = Q8((v - lo) / span * 255) corrected among k0 - 1, k0,
+ *                        k0 + 1 inside 0..255 as the centre code is
+ *
+ * st_ksplat_image_size (host only): the size above for sh_coeffs = C of the FILE; 0 for a C that
+ * is no band, a mode outside 0..2, n = 0, n >= 2^32 or a bucket count above n.
+ * st_dev_ksplat_plan: the plan of a device table (x, y, z of any types) on the device: dev_order[r]
+ * = the source row of record r, dev_bucket[r] = its bucket, dev_centres = 3 float32 per bucket,
+ * dev_partial_sizes = one u32 per partial bucket (all device, 4-byte aligned; order and bucket
+ * hold n entries, the bucket tables bucket_cap buckets: n is always enough).  *full, *partial and
+ * *out_clamped (nullable) come back; with more buckets than bucket_cap the call sets them, returns
+ * ST_ERR_ARG and writes no table.  Waits for the stream.
+ * st_dev_ksplat_records: records [rec0, rec0 + nrec) of the file at dev_out (device, ANY
+ * alignment), queued on the context stream.  The grid is the CALLER's here, so that a file's own
+ * bucket table can be handed in: dev_order (NULL: record r is row r), dev_bucket and dev_centres
+ * (modes 1 and 2; nbuckets entries; 4-byte aligned), any float32 block_size and any quant_range
+ * > 0 in place of B and 32767 (ps = block_size / 2 / quant_range; the public writer always uses B
+ * and 32767).  An order or bucket entry outside its table is the caller's error; it is read as the
+ * last row / bucket.
+ * st_dev_ksplat_image: the whole image at dev_out (device, any alignment).  *size = the bytes the
+ * image needs; above cap the call returns ST_ERR_ARG and writes nothing.
+ * No byte outside the stated output ranges is ever written by any of them.
+ * The file forms follow st_dev_spz_file / st_spz_file / st_ply_spz_file: the same descriptor checks
+ * before any work, the same processDataTable chain, the image built whole in HBM and copied down
+ * through the pinned ring, one device.
+ * Not written: more than one section, bucket capacities other than 256, an importance order of
+ * the rows, sharded output. */
+uint64_t st_ksplat_image_size(uint64_t n, int32_t sh_coeffs, int32_t mode, uint64_t full, uint64_t partial);
+int st_dev_ksplat_plan(st_ctx *ctx, const st_ttable *dev_table, float block_size, uint64_t bucket_cap,
+                       uint32_t *dev_order, uint32_t *dev_bucket, float *dev_centres, uint32_t *dev_partial_sizes,
+                       uint64_t *full, uint64_t *partial, uint64_t *out_clamped);
+int st_dev_ksplat_records(st_ctx *ctx, const st_ttable *dev_table, int32_t mode, int32_t degree, float sh_min,
+                          float sh_max, float block_size, uint32_t quant_range, const uint32_t *dev_order,
+                          const uint32_t *dev_bucket, const float *dev_centres, uint64_t nbuckets, uint64_t rec0,
+                          uint64_t nrec, uint8_t *dev_out);
+int st_dev_ksplat_image(st_ctx *ctx, const st_ttable *dev_table, int32_t mode, int32_t degree, float block_size,
+                        float sh_min, float sh_max, uint8_t *dev_out, uint64_t cap, uint64_t *size,
+                        uint64_t *out_clamped);
+int st_dev_ksplat_file(st_ctx *ctx, const st_ttable *dev_table, int32_t mode, int32_t degree, float block_size,
+                       float sh_min, float sh_max, int32_t out_fd, uint64_t *size, uint64_t *out_clamped);
+int st_ksplat_file(st_ctx *ctx, const st_ttable *src, const st_action *actions, int32_t nactions, int32_t mode,
+                   int32_t degree, float block_size, float sh_min, float sh_max, int32_t out_fd, uint64_t *out_m,
+                   uint64_t *size, uint64_t *out_clamped);
+int st_ply_ksplat_file(st_ctx *ctx, int32_t fd, const st_ply_header *h, int32_t element, const st_action *actions,
+                       int32_t nactions, int32_t mode, int32_t degree, float block_size, float sh_min, float sh_max,
+                       int32_t out_fd, uint64_t *out_m, uint64_t *size, uint64_t *out_clamped);
 
 #ifdef __cplusplus
 }

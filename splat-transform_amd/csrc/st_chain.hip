@@ -617,6 +617,37 @@ uint64_t spz_table_to_file(st_ctx *c, const st_ttable *t, int fractional_bits, i
     return size;
 }
 
+// the .ksplat image (headers, bucket tables, records) of a device table to fd from its position: built
+// whole in HBM -- it is smaller than the table it comes from -- and copied down through the ring
+uint64_t ksplat_table_to_file(st_ctx *c, const st_ttable *t, int mode, int degree, float block_size, float sh_min,
+                              float sh_max, int fd, uint64_t *clamped) {
+    const WrTable W = wr_table(t, true, "ksplat file");
+    const KswParams P = ksplat_params(W, mode, degree, block_size, sh_min, sh_max);
+    const uint64_t base = file_base(fd, "ksplat file");
+    const KswPlan K = ksplat_plan_begin(c, W, P.B);
+    if (clamped) *clamped = K.clamped;
+    const uint64_t size = ksplat_plan_image_size(K, P);
+    auto *image = wsT<uint8_t>(c, "ksw.image", size);
+    ksplat_image_from_plan(c, W, P, K, image);
+    {
+        FileRing ring(c, fd);
+        try {
+            for (uint64_t o = 0; o < size; o += ring.slot) {
+                const uint64_t nb = std::min(ring.slot, size - o);
+                uint8_t *host = ring.next();
+                if (!host) break;
+                ST_HIP(hipMemcpyAsync(host, image + o, nb, hipMemcpyDeviceToHost, c->stream));
+                ring.submit(nb, base + o);
+            }
+        } catch (...) {
+            ring.fail(std::current_exception());
+        }
+        ring.finish();
+    }
+    file_end(fd, base + size, "ksplat file");
+    return size;
+}
+
 // the host table into the chain
 auto host_loader(st_ctx *c, const st_ttable *src) {
     return [=](Chain &ch) {
@@ -1058,6 +1089,59 @@ int st_ply_spz_file(st_ctx *c, int32_t fd, const st_ply_header *h, int32_t eleme
         ply_chain(c, fd, h, element, ch);
         run_actions(ch, actions, nactions);
         *size = spz_table_to_file(c, ch.typed(), fractional_bits, out_fd, out_clamped);
+        *out_m = ch.n;
+    });
+}
+
+// the parameter checks that need no table, before any work (the table's own follow in ksplat_params)
+static void ksplat_arg_check(int32_t mode, int32_t degree, float block_size) {
+    ST_REQUIRE(mode >= 0 && mode <= 2, ST_ERR_ARG, "ksplat: mode must be 0, 1 or 2");
+    ST_REQUIRE(degree >= -1 && degree <= 3, ST_ERR_ARG, "ksplat: degree must be -1..3");
+    ST_REQUIRE(block_size > 0.0f && block_size < __builtin_inff(), ST_ERR_ARG,
+               "ksplat: block_size must be finite and > 0 as a float32");
+}
+
+int st_dev_ksplat_file(st_ctx *c, const st_ttable *t, int32_t mode, int32_t degree, float block_size, float sh_min,
+                       float sh_max, int32_t out_fd, uint64_t *size, uint64_t *out_clamped) {
+    return guard([&] {
+        ST_REQUIRE(c && t && size, ST_ERR_ARG, "NULL argument");
+        ksplat_arg_check(mode, degree, block_size);
+        check_src(t);
+        sog_file_check(out_fd);
+        use_device(c);
+        *size = ksplat_table_to_file(c, t, mode, degree, block_size, sh_min, sh_max, out_fd, out_clamped);
+    });
+}
+
+int st_ksplat_file(st_ctx *c, const st_ttable *src, const st_action *actions, int32_t nactions, int32_t mode,
+                   int32_t degree, float block_size, float sh_min, float sh_max, int32_t out_fd, uint64_t *out_m,
+                   uint64_t *size, uint64_t *out_clamped) {
+    return guard([&] {
+        ST_REQUIRE(c && src && out_m && size && (actions || nactions == 0), ST_ERR_ARG, "NULL argument");
+        ksplat_arg_check(mode, degree, block_size);
+        check_src(src);
+        sog_file_check(out_fd);
+        use_device(c);
+        Chain ch{c};
+        upload_chain(c, src, ch);
+        run_actions(ch, actions, nactions);
+        *size = ksplat_table_to_file(c, ch.typed(), mode, degree, block_size, sh_min, sh_max, out_fd, out_clamped);
+        *out_m = ch.n;
+    });
+}
+
+int st_ply_ksplat_file(st_ctx *c, int32_t fd, const st_ply_header *h, int32_t element, const st_action *actions,
+                       int32_t nactions, int32_t mode, int32_t degree, float block_size, float sh_min, float sh_max,
+                       int32_t out_fd, uint64_t *out_m, uint64_t *size, uint64_t *out_clamped) {
+    return guard([&] {
+        ST_REQUIRE(c && h && fd >= 0 && out_m && size && (actions || nactions == 0), ST_ERR_ARG, "NULL argument");
+        ksplat_arg_check(mode, degree, block_size);
+        sog_file_check(out_fd);
+        use_device(c);
+        Chain ch{c};
+        ply_chain(c, fd, h, element, ch);
+        run_actions(ch, actions, nactions);
+        *size = ksplat_table_to_file(c, ch.typed(), mode, degree, block_size, sh_min, sh_max, out_fd, out_clamped);
         *out_m = ch.n;
     });
 }

@@ -476,6 +476,32 @@ void spz_check(const WrTable &W, int fractional_bits);  // ST_ERR_ARG / ST_ERR_U
 // waits for the stream; *clamped (nullable) = the position values clamped.  Returns the size
 uint64_t spz_image_dev(st_ctx *c, const WrTable &W, int fractional_bits, uint8_t *out, uint64_t *clamped);
 
+// the .ksplat writer (st_ksplat_write.hip; the rules: st_abi.h, "the .ksplat writer").  ksplat_params
+// checks mode, degree (-1: the table's own), block size and harmonics range against a table picked
+// with_sh (ST_ERR_ARG / ST_ERR_UNSUPPORTED of the rules); modes 0 and 1 get the default range
+struct KswParams {
+    float B, sh_min, sh_max;
+    int mode, c_out;  // c_out: SH coefficients per channel of the file
+};
+KswParams ksplat_params(const WrTable &W, int mode, int degree, double block_size, float sh_min, float sh_max);
+uint64_t ksplat_image_size(uint64_t n, int C, int mode, uint64_t full, uint64_t partial);  // 0 for a bad argument
+// a plan in the workspace between its two steps: the sorted keys and rows, the cells' scans, and what
+// came back to the host
+struct KswPlan {
+    uint64_t n, F, P, clamped;
+    float B;
+    int sort_bits;  // key bits the sort went over
+    uint64_t *keys;
+    uint32_t *rows, *cid, *cstart, *fulloff, *partoff, *prow;
+    const void *stats;
+};
+// keys, sort and the scans over the cells: F, P and the clamp count are read back (waits for the stream)
+KswPlan ksplat_plan_begin(st_ctx *c, const WrTable &W, float B);
+uint64_t ksplat_plan_image_size(const KswPlan &K, const KswParams &P);
+// headers, bucket tables and records of a begun plan at out (device, any alignment,
+// ksplat_plan_image_size bytes); waits for the stream
+void ksplat_image_from_plan(st_ctx *c, const WrTable &W, const KswParams &P, const KswPlan &K, uint8_t *out);
+
 // the HTML viewer writer (write-html.ts, st_html.hip).  base64_dev queues k_base64 on the context
 // stream: the RFC 4648 text of bytes [byte0, byte0 + nbytes) of the stream that up to B64_MAX_SEGS
 // device segments make back to back, contiguous at out (device, 4-byte aligned).  base64_check

@@ -133,6 +133,8 @@ EXPORTS = [
     'st_dev_sog_read',
     'st_spz_image_size', 'st_dev_splat_rows', 'st_dev_spz_planes', 'st_dev_spz_image', 'st_dev_splat_file',
     'st_splat_file', 'st_ply_splat_file', 'st_dev_spz_file', 'st_spz_file', 'st_ply_spz_file',
+    'st_ksplat_image_size', 'st_dev_ksplat_plan', 'st_dev_ksplat_records', 'st_dev_ksplat_image', 'st_dev_ksplat_file',
+    'st_ksplat_file', 'st_ply_ksplat_file',
 ]
 
 
@@ -170,10 +172,12 @@ def lib():
         L.st_base64_size.argtypes = [ctypes.c_uint64]
         L.st_spz_image_size.restype = ctypes.c_uint64
         L.st_spz_image_size.argtypes = [ctypes.c_uint64, ctypes.c_int32]
+        L.st_ksplat_image_size.restype = ctypes.c_uint64
+        L.st_ksplat_image_size.argtypes = [ctypes.c_uint64, ctypes.c_int32, ctypes.c_int32, ctypes.c_uint64, ctypes.c_uint64]
         for name in EXPORTS:
             if name not in ('st_last_error', 'st_ctx_last_timings', 'st_ctx_last_kmeans_stats', 'st_ctx_destroy', 'st_free', 'st_webp_max_size',
                             'st_ply_row_bytes', 'st_csv_max_row_bytes', 'st_base64_size', 'st_comm_destroy',
-                            'st_group_destroy', 'st_spz_image_size'):
+                            'st_group_destroy', 'st_spz_image_size', 'st_ksplat_image_size'):
                 getattr(L, name).restype = ctypes.c_int
         _lib = L
     return _lib
@@ -707,6 +711,13 @@ def spz_image_size(n, sh_coeffs):
     """the bytes of a raw .spz image of n splats with sh_coeffs (0, 3, 8 or 15) coefficients per
     channel: 16 + n * (19 + 3 * sh_coeffs); 0 for a bad argument (st_spz_image_size; host only)"""
     return lib().st_spz_image_size(ctypes.c_uint64(n), ctypes.c_int32(sh_coeffs))
+
+
+def ksplat_image_size(n, sh_coeffs, mode, full, partial):
+    """the bytes of a .ksplat image of n splats in `full` + `partial` buckets with sh_coeffs (0, 3, 8 or
+    15) coefficients per channel in the file: 5120 + 4 partial + 12 (full + partial) + n * stride; 0 for
+    a bad argument (st_ksplat_image_size; host only)"""
+    return lib().st_ksplat_image_size(n, sh_coeffs, mode, full, partial)
 
 
 SPZ_DEFLATE_SEGMENT = 8 << 20
@@ -1853,6 +1864,96 @@ class Context:
                 os.close(fd)
             return m.value, size.value, clamped.value
         return self._spz_out(call, out, gzip_level)
+
+    # ---- the .ksplat writer (st_abi.h, "the .ksplat writer") -------------------------------------
+    def dev_ksplat_plan(self, cols, block_size=5.0):
+        """st_dev_ksplat_plan: the bucket plan of device columns (x, y, z of any types) -> a dict of
+        device tensors and counts: order (source row of each record), bucket (of each record), centres
+        [F + P, 3] float32, partial_sizes [P], full, partial, clamped"""
+        import torch
+        t = make_ttable(cols)
+        items = list(cols.items()) if isinstance(cols, dict) else list(cols)
+        dev = items[0][1].device
+        n = max(t.n, 1)
+        order = torch.empty(n, dtype=torch.int32, device=dev)
+        bucket = torch.empty(n, dtype=torch.int32, device=dev)
+        centres = torch.empty(3 * n, dtype=torch.float32, device=dev)
+        sizes = torch.empty(n, dtype=torch.int32, device=dev)
+        full, partial, clamped = ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_uint64()
+        check(lib().st_dev_ksplat_plan(self.h, ctypes.byref(t), ctypes.c_float(block_size), ctypes.c_uint64(n), _ptr(order),
+                                       _ptr(bucket), _ptr(centres), _ptr(sizes), ctypes.byref(full), ctypes.byref(partial),
+                                       ctypes.byref(clamped)))
+        nb = full.value + partial.value
+        return dict(order=order[:t.n], bucket=bucket[:t.n], centres=centres[:3 * nb].reshape(nb, 3),
+                    partial_sizes=sizes[:partial.value], full=full.value, partial=partial.value, clamped=clamped.value)
+
+    def dev_ksplat_records(self, cols, out, mode, order, bucket, centres, degree=-1, block_size=5.0, quant_range=32767,
+                           sh_min=-1.5, sh_max=1.5, rec0=0, nrec=None):
+        """st_dev_ksplat_records: records [rec0, rec0 + nrec) of device columns at `out`, a device uint8
+        tensor of any alignment, through the caller's grid: order (int32 tensor or None: record r is row
+        r), bucket (of each record) and centres (float32, 3 per bucket) -- None in mode 0 --, the block
+        size and the quantisation range"""
+        t = make_ttable(cols)
+        if nrec is None:
+            nrec = t.n - rec0
+        nb = centres.numel() // 3 if centres is not None else 0
+        check(lib().st_dev_ksplat_records(self.h, ctypes.byref(t), ctypes.c_int32(mode), ctypes.c_int32(degree),
+                                          ctypes.c_float(sh_min), ctypes.c_float(sh_max), ctypes.c_float(block_size),
+                                          ctypes.c_uint32(quant_range), _ptr(order), _ptr(bucket), _ptr(centres),
+                                          ctypes.c_uint64(nb), ctypes.c_uint64(rec0), ctypes.c_uint64(nrec), _ptr(out)))
+
+    def dev_ksplat_image(self, cols, out, mode=1, degree=-1, block_size=5.0, sh_min=-1.5, sh_max=1.5):
+        """st_dev_ksplat_image: the whole .ksplat image of device columns at `out`, a device uint8 tensor
+        of any alignment -> (bytes the image needs, position values clamped).  A tensor too small raises
+        ST_ERR_ARG and is left untouched"""
+        t = make_ttable(cols)
+        size, clamped = ctypes.c_uint64(), ctypes.c_uint64()
+        check(lib().st_dev_ksplat_image(self.h, ctypes.byref(t), ctypes.c_int32(mode), ctypes.c_int32(degree),
+                                        ctypes.c_float(block_size), ctypes.c_float(sh_min), ctypes.c_float(sh_max), _ptr(out),
+                                        ctypes.c_uint64(out.numel()), ctypes.byref(size), ctypes.byref(clamped)))
+        return size.value, clamped.value
+
+    def dev_ksplat_file(self, cols, out, mode=1, degree=-1, block_size=5.0, sh_min=-1.5, sh_max=1.5):
+        """a table already in HBM (list of (name, tensor) or a dict) as a .ksplat file in `out`, a path or
+        a descriptor (written from its position): (rows, file bytes, position values clamped)"""
+        t = make_ttable(cols)
+        size, clamped = ctypes.c_uint64(), ctypes.c_uint64()
+        with _OutFd(out) as fd:
+            check(lib().st_dev_ksplat_file(self.h, ctypes.byref(t), ctypes.c_int32(mode), ctypes.c_int32(degree),
+                                           ctypes.c_float(block_size), ctypes.c_float(sh_min), ctypes.c_float(sh_max), fd,
+                                           ctypes.byref(size), ctypes.byref(clamped)))
+        return t.n, size.value, clamped.value
+
+    def ksplat_file(self, cols, actions, out, mode=1, degree=-1, block_size=5.0, sh_min=-1.5, sh_max=1.5):
+        """processDataTable + the .ksplat writer on a host table (list of (name, numpy array) or a dict)
+        into `out` (st_ksplat_file): (rows written, file bytes, position values clamped)"""
+        items = list(cols.items()) if isinstance(cols, dict) else list(cols)
+        ts = make_ttable(items, len(items[0][1]) if items else 0)
+        acts = make_actions(actions)
+        m, size, clamped = ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_uint64()
+        with _OutFd(out) as fd:
+            check(lib().st_ksplat_file(self.h, ctypes.byref(ts), acts, ctypes.c_int32(len(actions)), ctypes.c_int32(mode),
+                                       ctypes.c_int32(degree), ctypes.c_float(block_size), ctypes.c_float(sh_min),
+                                       ctypes.c_float(sh_max), fd, ctypes.byref(m), ctypes.byref(size), ctypes.byref(clamped)))
+        return m.value, size.value, clamped.value
+
+    def ply_ksplat_file(self, path, actions, out, mode=1, degree=-1, block_size=5.0, sh_min=-1.5, sh_max=1.5, element=-1):
+        """`in.ply [actions] out.ksplat` (st_ply_ksplat_file): the element's rows stay in HBM from ingest
+        to the image: (rows written, file bytes, position values clamped)"""
+        acts = make_actions(actions)
+        fd = os.open(path, os.O_RDONLY)
+        try:
+            h = PlyHeader()
+            check(lib().st_ply_read_header(ctypes.c_int32(fd), ctypes.byref(h)))
+            m, size, clamped = ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_uint64()
+            with _OutFd(out) as ofd:
+                check(lib().st_ply_ksplat_file(self.h, ctypes.c_int32(fd), ctypes.byref(h), ctypes.c_int32(element), acts,
+                                               ctypes.c_int32(len(actions)), ctypes.c_int32(mode), ctypes.c_int32(degree),
+                                               ctypes.c_float(block_size), ctypes.c_float(sh_min), ctypes.c_float(sh_max), ofd,
+                                               ctypes.byref(m), ctypes.byref(size), ctypes.byref(clamped)))
+        finally:
+            os.close(fd)
+        return m.value, size.value, clamped.value
 
     # ---- writeHtml (write-html.ts) -------------------------------------------------------
     def dev_base64(self, segs, out, byte0=0, nbytes=None):
