@@ -899,7 +899,7 @@ int st_dev_sog_read(st_ctx *ctx, const uint8_t *data, uint64_t len, const st_sog
  * once; the .spz forms write the RAW image, built whole in HBM: what readSpz decodes after its
  * gunzip (st_spz_layout / st_spz_read take it as is).  The gzip member around it, which readSpz
  * itself (read-spz.ts:56-75 stops on a file without the gzip magic) and other .spz consumers
- * expect, is the caller's, as gunzip is for the reader. */
+ * expect, is the caller's here; the st_*_spz_gz_file forms below write it. */
 uint64_t st_spz_image_size(uint64_t n, int32_t sh_coeffs);
 int st_dev_splat_rows(st_ctx *ctx, const st_ttable *dev_table, uint64_t row0, uint64_t nrows, uint8_t *dev_rows);
 int st_dev_spz_planes(st_ctx *ctx, const st_ttable *dev_table, int32_t fractional_bits, uint64_t row0,
@@ -918,6 +918,57 @@ int st_spz_file(st_ctx *ctx, const st_ttable *src, const st_action *actions, int
 int st_ply_spz_file(st_ctx *ctx, int32_t fd, const st_ply_header *h, int32_t element, const st_action *actions,
                     int32_t nactions, int32_t fractional_bits, int32_t out_fd, uint64_t *out_m, uint64_t *size,
                     uint64_t *out_clamped);
+
+/* ---- the gzip member around a .spz image: DEFLATE (RFC 1951) on the device ---------------------
+ * readSpz takes a gzip member (read-spz.ts:56-75 stops on a file without the gzip magic); the raw
+ * forms above leave it to the caller.  These make it on the device.  The stream is this project's
+ * own choice among the valid ones, fixed by the rules below, so a host program that follows them
+ * (csrc/st_deflate.h's serial encoder) gives the same bytes.
+ *
+ * Segments.  The input is cut into segments of ST_DEFLATE_SEG bytes, each coded alone: no token
+ * refers to bytes before its segment.  Every segment's code ends on a byte boundary: a segment
+ * that is not the last and is not stored is followed by an empty stored block (bits 000, zero
+ * padding to the byte, then 00 00 FF FF); the last block of the last segment has BFINAL = 1 and is
+ * padded with zeros.  n = 0 is the one fixed block 03 00.
+ * Tokens are literals and matches of distance 1.  Of a maximal run of L equal bytes inside a
+ * segment the first byte is a literal; the other L - 1 are cut greedily into matches of 258; a
+ * remainder of at least 3 is one match, a remainder of 1 or 2 is literals.
+ * Block type.  A segment is the smallest, in bytes with its byte-boundary trailer, of: stored
+ * blocks (LEN at most 65,535, so a full segment takes two); one fixed-code block; one
+ * dynamic-code block.  Ties go to the simpler coding, in that order.
+ * Dynamic blocks.  Literal/length code: Huffman's tree over the used symbols and one end-of-block,
+ * merged from the symbols in (count, symbol) order, of two equal weights the internal node first;
+ * if it is deeper than 15, counts are raised to a floor that doubles from
+ * max(2, total >> 17) until it is not.  Distance symbols 0 and 1 both get length 1 (HDIST = 2).
+ * The lengths of both codes form one sequence, coded with 16 / 17 / 18: a run of zeros is cut
+ * greedily into 18s (11..138), a 17 (3..10), then single zeros; a run of another length is that
+ * length once, 16s (3..6), then the length again for the rest.  The code-length code is built the
+ * same way with the limit 7 and the floor from max(2, total >> 9).  Codes are canonical, written
+ * MSB-first into the LSB-first stream; extra bits go LSB-first.
+ *
+ * st_deflate_bound(n): the all-stored size, which is also the stream's worst case; 2 for n = 0.
+ * st_gzip_bound(n) = st_deflate_bound(n) + 18.
+ * st_dev_deflate: the stream of dev_in[0..n) at dev_out, *size = its bytes.  dev_in and dev_out are
+ * device pointers of ANY alignment; no byte outside [dev_out, dev_out + *size) is written; if the
+ * stream does not fit cap, nothing is written and the call returns ST_ERR_ARG (against the bound
+ * that never happens).  All offsets are 64-bit.  Waits for the kernels (the size).
+ * st_dev_gzip: one gzip member: 1f 8b 08 00 00 00 00 00 00 ff, the stream, the CRC-32 of the
+ * input, n mod 2^32.
+ * st_dev_spz_gz_file / st_spz_gz_file / st_ply_spz_gz_file: st_dev_spz_file / st_spz_file /
+ * st_ply_spz_file with the member around the image: the same arguments, descriptor rules and ring;
+ * the raw image and the member are both built in HBM; *size = the file's bytes. */
+#define ST_DEFLATE_SEG 65536
+uint64_t st_deflate_bound(uint64_t n);
+uint64_t st_gzip_bound(uint64_t n);
+int st_dev_deflate(st_ctx *ctx, const uint8_t *dev_in, uint64_t n, uint8_t *dev_out, uint64_t cap, uint64_t *size);
+int st_dev_gzip(st_ctx *ctx, const uint8_t *dev_in, uint64_t n, uint8_t *dev_out, uint64_t cap, uint64_t *size);
+int st_dev_spz_gz_file(st_ctx *ctx, const st_ttable *dev_table, int32_t fractional_bits, int32_t out_fd,
+                       uint64_t *size, uint64_t *out_clamped);
+int st_spz_gz_file(st_ctx *ctx, const st_ttable *src, const st_action *actions, int32_t nactions,
+                   int32_t fractional_bits, int32_t out_fd, uint64_t *out_m, uint64_t *size, uint64_t *out_clamped);
+int st_ply_spz_gz_file(st_ctx *ctx, int32_t fd, const st_ply_header *h, int32_t element, const st_action *actions,
+                       int32_t nactions, int32_t fractional_bits, int32_t out_fd, uint64_t *out_m, uint64_t *size,
+                       uint64_t *out_clamped);
 
 /* ---- the .ksplat writer (no reference counterpart: the reference reads the format,
  * readers/read-ksplat.ts:103-384, and has no writer for it) ---------------------------------------

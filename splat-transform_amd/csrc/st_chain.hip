@@ -590,14 +590,22 @@ uint64_t splat_table_to_file(st_ctx *c, const st_ttable *t, int fd) {
 }
 
 // the raw .spz image (header + six planes) of a device table to fd from its position: built whole
-// in HBM -- it is smaller than the table it comes from -- and copied down through the ring
-uint64_t spz_table_to_file(st_ctx *c, const st_ttable *t, int fractional_bits, int fd, uint64_t *clamped) {
+// in HBM -- it is smaller than the table it comes from -- and copied down through the ring.  gz: the
+// gzip member around the image (st_deflate.hip), made in HBM beside it, is what goes down
+uint64_t spz_table_to_file(st_ctx *c, const st_ttable *t, int fractional_bits, int fd, uint64_t *clamped,
+                           bool gz = false) {
     const WrTable W = wr_table(t, true, "spz file");
     spz_check(W, fractional_bits);
     const uint64_t base = file_base(fd, "spz file");
-    const uint64_t size = spz_image_size(W.n, W.C);
+    uint64_t size = spz_image_size(W.n, W.C);
     auto *image = wsT<uint8_t>(c, "spzw.image", size);
     spz_image_dev(c, W, fractional_bits, image, clamped);
+    if (gz) {
+        const uint64_t cap = st_gzip_bound(size);
+        auto *member = wsT<uint8_t>(c, "spzw.gz", cap);
+        size = gzip_dev(c, image, size, member, cap);
+        image = member;
+    }
     {
         FileRing ring(c, fd);
         try {
@@ -1089,6 +1097,51 @@ int st_ply_spz_file(st_ctx *c, int32_t fd, const st_ply_header *h, int32_t eleme
         ply_chain(c, fd, h, element, ch);
         run_actions(ch, actions, nactions);
         *size = spz_table_to_file(c, ch.typed(), fractional_bits, out_fd, out_clamped);
+        *out_m = ch.n;
+    });
+}
+
+// the same three with the gzip member around the image, deflated on the device
+int st_dev_spz_gz_file(st_ctx *c, const st_ttable *t, int32_t fractional_bits, int32_t out_fd, uint64_t *size,
+                       uint64_t *out_clamped) {
+    return guard([&] {
+        ST_REQUIRE(c && t && size, ST_ERR_ARG, "NULL argument");
+        ST_REQUIRE(fractional_bits >= 0 && fractional_bits <= 23, ST_ERR_ARG, "spz: fractional_bits must be 0..23");
+        check_src(t);
+        sog_file_check(out_fd);
+        use_device(c);
+        *size = spz_table_to_file(c, t, fractional_bits, out_fd, out_clamped, true);
+    });
+}
+
+int st_spz_gz_file(st_ctx *c, const st_ttable *src, const st_action *actions, int32_t nactions,
+                   int32_t fractional_bits, int32_t out_fd, uint64_t *out_m, uint64_t *size, uint64_t *out_clamped) {
+    return guard([&] {
+        ST_REQUIRE(c && src && out_m && size && (actions || nactions == 0), ST_ERR_ARG, "NULL argument");
+        ST_REQUIRE(fractional_bits >= 0 && fractional_bits <= 23, ST_ERR_ARG, "spz: fractional_bits must be 0..23");
+        check_src(src);
+        sog_file_check(out_fd);
+        use_device(c);
+        Chain ch{c};
+        upload_chain(c, src, ch);
+        run_actions(ch, actions, nactions);
+        *size = spz_table_to_file(c, ch.typed(), fractional_bits, out_fd, out_clamped, true);
+        *out_m = ch.n;
+    });
+}
+
+int st_ply_spz_gz_file(st_ctx *c, int32_t fd, const st_ply_header *h, int32_t element, const st_action *actions,
+                       int32_t nactions, int32_t fractional_bits, int32_t out_fd, uint64_t *out_m, uint64_t *size,
+                       uint64_t *out_clamped) {
+    return guard([&] {
+        ST_REQUIRE(c && h && fd >= 0 && out_m && size && (actions || nactions == 0), ST_ERR_ARG, "NULL argument");
+        ST_REQUIRE(fractional_bits >= 0 && fractional_bits <= 23, ST_ERR_ARG, "spz: fractional_bits must be 0..23");
+        sog_file_check(out_fd);
+        use_device(c);
+        Chain ch{c};
+        ply_chain(c, fd, h, element, ch);
+        run_actions(ch, actions, nactions);
+        *size = spz_table_to_file(c, ch.typed(), fractional_bits, out_fd, out_clamped, true);
         *out_m = ch.n;
     });
 }

@@ -475,6 +475,10 @@ void spz_check(const WrTable &W, int fractional_bits);  // ST_ERR_ARG / ST_ERR_U
 // header + six planes of the whole table at out (device, any alignment, spz_image_size bytes);
 // waits for the stream; *clamped (nullable) = the position values clamped.  Returns the size
 uint64_t spz_image_dev(st_ctx *c, const WrTable &W, int fractional_bits, uint8_t *out, uint64_t *clamped);
+// st_deflate.hip: the RFC 1951 stream / the gzip member of dev_in[0..n) at dev_out (any alignment);
+// returns its size; above cap: ST_ERR_ARG and nothing is written.  Both wait for their kernels.
+uint64_t deflate_dev(st_ctx *c, const uint8_t *dev_in, uint64_t n, uint8_t *dev_out, uint64_t cap);
+uint64_t gzip_dev(st_ctx *c, const uint8_t *dev_in, uint64_t n, uint8_t *dev_out, uint64_t cap);
 
 // the .ksplat writer (st_ksplat_write.hip; the rules: st_abi.h, "the .ksplat writer").  ksplat_params
 // checks mode, degree (-1: the table's own), block size and harmonics range against a table picked

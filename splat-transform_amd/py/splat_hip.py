@@ -135,6 +135,8 @@ EXPORTS = [
     'st_splat_file', 'st_ply_splat_file', 'st_dev_spz_file', 'st_spz_file', 'st_ply_spz_file',
     'st_ksplat_image_size', 'st_dev_ksplat_plan', 'st_dev_ksplat_records', 'st_dev_ksplat_image', 'st_dev_ksplat_file',
     'st_ksplat_file', 'st_ply_ksplat_file',
+    'st_deflate_bound', 'st_gzip_bound', 'st_dev_deflate', 'st_dev_gzip', 'st_dev_spz_gz_file', 'st_spz_gz_file',
+    'st_ply_spz_gz_file',
 ]
 
 
@@ -174,10 +176,14 @@ def lib():
         L.st_spz_image_size.argtypes = [ctypes.c_uint64, ctypes.c_int32]
         L.st_ksplat_image_size.restype = ctypes.c_uint64
         L.st_ksplat_image_size.argtypes = [ctypes.c_uint64, ctypes.c_int32, ctypes.c_int32, ctypes.c_uint64, ctypes.c_uint64]
+        for name in ('st_deflate_bound', 'st_gzip_bound'):
+            getattr(L, name).restype = ctypes.c_uint64
+            getattr(L, name).argtypes = [ctypes.c_uint64]
         for name in EXPORTS:
             if name not in ('st_last_error', 'st_ctx_last_timings', 'st_ctx_last_kmeans_stats', 'st_ctx_destroy', 'st_free', 'st_webp_max_size',
                             'st_ply_row_bytes', 'st_csv_max_row_bytes', 'st_base64_size', 'st_comm_destroy',
-                            'st_group_destroy', 'st_spz_image_size', 'st_ksplat_image_size'):
+                            'st_group_destroy', 'st_spz_image_size', 'st_ksplat_image_size', 'st_deflate_bound',
+                            'st_gzip_bound'):
                 getattr(L, name).restype = ctypes.c_int
         _lib = L
     return _lib
@@ -752,6 +758,19 @@ def spz_deflate(raw, level, threads=8, _segment=SPZ_DEFLATE_SEGMENT):
     return head + b''.join(parts) + (crc & 0xffffffff).to_bytes(4, 'little') + (len(raw) & 0xffffffff).to_bytes(4, 'little')
 
 
+DEFLATE_SEG = 65536  # ST_DEFLATE_SEG
+
+
+def deflate_bound(n):
+    """st_deflate_bound: the most bytes Context.dev_deflate writes for n input bytes"""
+    return lib().st_deflate_bound(n)
+
+
+def gzip_bound(n):
+    """st_gzip_bound: the most bytes Context.dev_gzip writes for n input bytes"""
+    return lib().st_gzip_bound(n)
+
+
 # ---- the .sog reader's host pieces ------------------------------------------------------------
 class ZipEntry(ctypes.Structure):
     _fields_ = [('name_offset', ctypes.c_uint64), ('name_len', ctypes.c_uint32), ('crc', ctypes.c_uint32),
@@ -1192,6 +1211,22 @@ class Context:
         check(lib().st_dev_crc32(self.h, _ptr(data), ctypes.c_uint64(n), ctypes.c_uint32(crc_in),
                                  ctypes.byref(out)))
         return out.value
+
+    def _dev_deflate(self, fn, data, out, n):
+        n = data.numel() if n is None else n
+        size = ctypes.c_uint64(0)
+        check(fn(self.h, _ptr(data), ctypes.c_uint64(n), _ptr(out), ctypes.c_uint64(out.numel()), ctypes.byref(size)))
+        return size.value
+
+    def dev_deflate(self, data, out, n=None):
+        """st_dev_deflate: the RFC 1951 stream (st_abi.h's rules) of the first n bytes of the device
+        uint8 tensor `data` into the device uint8 tensor `out`, both of any alignment -> its bytes.
+        A tensor too small raises ST_ERR_ARG and is left untouched"""
+        return self._dev_deflate(lib().st_dev_deflate, data, out, n)
+
+    def dev_gzip(self, data, out, n=None):
+        """st_dev_gzip: one gzip member around that stream (spz_deflate's header, CRC-32, size)"""
+        return self._dev_deflate(lib().st_dev_gzip, data, out, n)
 
     def dev_sog_bundle_view(self, meta, count, tex, dos_time, dos_date):
         """as dev_sog_bundle without the copy: (address, size) of the context's pinned archive"""
@@ -1783,14 +1818,18 @@ class Context:
         return m.value, size.value
 
     @staticmethod
-    def _spz_out(call, out, gzip_level):
-        """call(fd) runs a .spz file form into a descriptor and returns (rows, raw bytes, clamped).
-        gzip_level 0: straight into `out`.  Otherwise the raw image goes into an anonymous memory
+    def _spz_out(call, out, gzip_level, deflate='host'):
+        """call(fd, gz) runs a .spz file form (gz: its st_*_gz_file twin) into a descriptor and returns
+        (rows, bytes, clamped).  gzip_level 0: the raw form straight into `out`.  deflate='device': the
+        gz form straight into `out`, the member made on the device (any non-zero level: the stream is
+        fixed by st_abi.h's rules).  Otherwise (deflate='host') the raw image goes into an anonymous memory
         file, spz_deflate makes the one gzip member and that is written at out's position, under the
         library's rules for an output descriptor: (rows, file bytes, clamped)"""
-        if gzip_level == 0:
+        if deflate not in ('host', 'device'):
+            raise ValueError("deflate must be 'host' or 'device'")
+        if gzip_level == 0 or deflate == 'device':
             with _OutFd(out) as fd:
-                return call(fd)
+                return call(fd, gzip_level != 0)
         import fcntl
         import mmap
         with _OutFd(out) as fd:
@@ -1803,7 +1842,7 @@ class Context:
                 raise StError(ST_ERR_ARG, 'spz file: the output descriptor must be open for writing, not O_APPEND')
             mfd = os.memfd_create('spz_raw')
             try:
-                rows, size, clamped = call(ctypes.c_int32(mfd))
+                rows, size, clamped = call(ctypes.c_int32(mfd), False)
                 mm = mmap.mmap(mfd, size, access=mmap.ACCESS_READ)
                 try:
                     member = spz_deflate(mm, gzip_level)
@@ -1818,52 +1857,57 @@ class Context:
             os.lseek(fd.value, pos + len(member), os.SEEK_SET)
             return rows, len(member), clamped
 
-    def dev_spz_file(self, cols, out, fractional_bits=12, gzip_level=6):
+    def dev_spz_file(self, cols, out, fractional_bits=12, gzip_level=6, deflate='host'):
         """a table already in HBM (list of (name, tensor) or a dict) as a .spz file in `out`, a path or
         a descriptor (written from its position): (rows, file bytes, position values clamped).
-        gzip_level 0 writes the raw image; otherwise one gzip member around it (spz_deflate)"""
+        gzip_level 0 writes the raw image; otherwise one gzip member around it: deflate='host' makes it
+        with spz_deflate at that level, deflate='device' on the device (st_dev_spz_gz_file)"""
         t = make_ttable(cols)
 
-        def call(fd):
+        def call(fd, gz):
             size, clamped = ctypes.c_uint64(), ctypes.c_uint64()
-            check(lib().st_dev_spz_file(self.h, ctypes.byref(t), ctypes.c_int32(fractional_bits), fd, ctypes.byref(size),
-                                        ctypes.byref(clamped)))
+            form = lib().st_dev_spz_gz_file if gz else lib().st_dev_spz_file
+            check(form(self.h, ctypes.byref(t), ctypes.c_int32(fractional_bits), fd, ctypes.byref(size),
+                       ctypes.byref(clamped)))
             return t.n, size.value, clamped.value
-        return self._spz_out(call, out, gzip_level)
+        return self._spz_out(call, out, gzip_level, deflate)
 
-    def spz_file(self, cols, actions, out, fractional_bits=12, gzip_level=6):
+    def spz_file(self, cols, actions, out, fractional_bits=12, gzip_level=6, deflate='host'):
         """processDataTable + the .spz writer on a host table (list of (name, numpy array) or a dict)
-        into `out` (st_spz_file): (rows written, file bytes, position values clamped)"""
+        into `out` (st_spz_file; deflate='device': st_spz_gz_file): (rows written, file bytes, position
+        values clamped)"""
         items = list(cols.items()) if isinstance(cols, dict) else list(cols)
         ts = make_ttable(items, len(items[0][1]) if items else 0)
         acts = make_actions(actions)
 
-        def call(fd):
+        def call(fd, gz):
             m, size, clamped = ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_uint64()
-            check(lib().st_spz_file(self.h, ctypes.byref(ts), acts, ctypes.c_int32(len(actions)),
-                                    ctypes.c_int32(fractional_bits), fd, ctypes.byref(m), ctypes.byref(size),
-                                    ctypes.byref(clamped)))
+            form = lib().st_spz_gz_file if gz else lib().st_spz_file
+            check(form(self.h, ctypes.byref(ts), acts, ctypes.c_int32(len(actions)), ctypes.c_int32(fractional_bits),
+                       fd, ctypes.byref(m), ctypes.byref(size), ctypes.byref(clamped)))
             return m.value, size.value, clamped.value
-        return self._spz_out(call, out, gzip_level)
+        return self._spz_out(call, out, gzip_level, deflate)
 
-    def ply_spz_file(self, path, actions, out, fractional_bits=12, gzip_level=6, element=-1):
+    def ply_spz_file(self, path, actions, out, fractional_bits=12, gzip_level=6, element=-1, deflate='host'):
         """`in.ply [actions] out.spz` (st_ply_spz_file): the element's rows stay in HBM from ingest to
-        the image: (rows written, file bytes, position values clamped)"""
+        the image (deflate='device': to the gzip member, st_ply_spz_gz_file): (rows written, file bytes,
+        position values clamped)"""
         acts = make_actions(actions)
 
-        def call(ofd):
+        def call(ofd, gz):
             fd = os.open(path, os.O_RDONLY)
             try:
                 h = PlyHeader()
                 check(lib().st_ply_read_header(ctypes.c_int32(fd), ctypes.byref(h)))
                 m, size, clamped = ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_uint64()
-                check(lib().st_ply_spz_file(self.h, ctypes.c_int32(fd), ctypes.byref(h), ctypes.c_int32(element), acts,
-                                            ctypes.c_int32(len(actions)), ctypes.c_int32(fractional_bits), ofd,
-                                            ctypes.byref(m), ctypes.byref(size), ctypes.byref(clamped)))
+                form = lib().st_ply_spz_gz_file if gz else lib().st_ply_spz_file
+                check(form(self.h, ctypes.c_int32(fd), ctypes.byref(h), ctypes.c_int32(element), acts,
+                           ctypes.c_int32(len(actions)), ctypes.c_int32(fractional_bits), ofd, ctypes.byref(m),
+                           ctypes.byref(size), ctypes.byref(clamped)))
             finally:
                 os.close(fd)
             return m.value, size.value, clamped.value
-        return self._spz_out(call, out, gzip_level)
+        return self._spz_out(call, out, gzip_level, deflate)
 
     # ---- the .ksplat writer (st_abi.h, "the .ksplat writer") -------------------------------------
     def dev_ksplat_plan(self, cols, block_size=5.0):
