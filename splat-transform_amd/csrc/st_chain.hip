@@ -351,6 +351,44 @@ struct FileRing {
     ~FileRing() { stop(); }
 };
 
+// one piece of a file's body: `bytes` for file offset `off`; no bytes: the body has ended
+struct Part {
+    uint64_t bytes, off;
+};
+
+// a file's body through the ring, piece by piece: plan(k) sizes piece k (it may wait for the device
+// to learn the size), source(k) queues the device work that makes the piece and returns where its
+// bytes will be in HBM; the copy into the pinned slot follows them on the context's stream.  plan
+// runs before the slot is waited for and source after, so a ring already in error gets no more
+// work queued.  An error in here goes to the ring, whose finish() rethrows it.
+template <typename Plan, typename Source>
+void pump(FileRing &ring, Plan plan, Source source) {
+    try {
+        for (uint64_t k = 0;; ++k) {
+            const Part p = plan(k);
+            if (!p.bytes) break;
+            uint8_t *host = ring.next();
+            if (!host) break;
+            const uint8_t *dev = source(k);
+            ST_HIP(hipMemcpyAsync(host, dev, p.bytes, hipMemcpyDeviceToHost, ring.c->stream));
+            ring.submit(p.bytes, p.off);
+        }
+    } catch (...) {
+        ring.fail(std::current_exception());
+    }
+}
+
+// bytes that lie whole in HBM to file offset `off`, one ring slot a piece
+void device_bytes_to_file(FileRing &ring, const uint8_t *dev, uint64_t bytes, uint64_t off) {
+    pump(
+        ring,
+        [&](uint64_t k) {
+            const uint64_t o = k * ring.slot;
+            return Part{o < bytes ? std::min(ring.slot, bytes - o) : 0, off + o};
+        },
+        [&](uint64_t k) { return dev + k * ring.slot; });
+}
+
 // the output's first byte: the descriptor's position, as the reference's FileHandle.write calls go
 // (the CLI's fresh output: 0)
 uint64_t file_base(int fd, const char *what) {
@@ -365,6 +403,23 @@ void file_end(int fd, uint64_t total, const char *what) {
     ST_REQUIRE(lseek(fd, (off_t)total, SEEK_SET) == (off_t)total, ST_ERR_ARG, std::string(what) + ": lseek failed");
 }
 
+// writeCompressedPly's arrays of the chain's table, in workspace slots: m rows, C coefficients a channel
+struct CplyArrays {
+    uint64_t m;
+    int32_t C;
+    float *chunk;
+    uint32_t *vert;
+    uint8_t *sh;
+};
+CplyArrays compressed_arrays(Chain &ch) {
+    st_ctx *c = ch.c;
+    const uint64_t m = ch.n, nch = (m + 255) / 256;
+    CplyArrays a{m, 0, wsT<float>(c, "chain.chunk", nch * 18), wsT<uint32_t>(c, "chain.vert", m * 4),
+                 wsT<uint8_t>(c, "chain.sh", m * 3 * (uint64_t)ch.coeffs() + 1)};
+    compressed_tail(ch, a.chunk, a.vert, a.sh, &a.C);
+    return a;
+}
+
 // what follows the header in a .compressed.ply file (write-compressed-ply.ts:112-114): the chunk,
 // vertex and sh arrays in HBM, in file order, the empty ones left out; `off` = a region's first
 // byte counted from the header's end
@@ -372,43 +427,30 @@ struct Region {
     const uint8_t *dev;
     uint64_t bytes, off;
 };
-std::vector<Region> compressed_ply_regions(uint64_t m, int C, const float *dchunk, const uint32_t *dvert,
-                                           const uint8_t *dsh) {
-    const uint64_t nch = (m + 255) / 256;
+std::vector<Region> compressed_ply_regions(const CplyArrays &a) {
+    const uint64_t nch = (a.m + 255) / 256;
     std::vector<Region> rs;
     uint64_t off = 0;
-    for (const Region &r : {Region{reinterpret_cast<const uint8_t *>(dchunk), nch * 72, 0},
-                            Region{reinterpret_cast<const uint8_t *>(dvert), m * 16, 0},
-                            Region{dsh, C ? m * 3 * (uint64_t)C : 0, 0}}) {
+    for (const Region &r : {Region{reinterpret_cast<const uint8_t *>(a.chunk), nch * 72, 0},
+                            Region{reinterpret_cast<const uint8_t *>(a.vert), a.m * 16, 0},
+                            Region{a.sh, a.C ? a.m * 3 * (uint64_t)a.C : 0, 0}}) {
         if (r.bytes) rs.push_back({r.dev, r.bytes, off});
         off += r.bytes;
     }
     return rs;
 }
 
-// the device arrays to fd at offsets from its position through the ring; the file ends at the last byte
-uint64_t compressed_ply_to_file(st_ctx *c, uint64_t m, int C, const float *dchunk, const uint32_t *dvert,
-                                const uint8_t *dsh, int fd, const char *version) {
-    const std::string head = compressed_ply_header(m, C, version);
+// the device arrays to fd at offsets from its position through the ring (one writer thread for
+// the whole file); the file ends at the last byte
+uint64_t compressed_ply_to_file(st_ctx *c, const CplyArrays &a, int fd, const char *version) {
+    const std::string head = compressed_ply_header(a.m, a.C, version);
     const uint64_t base = file_base(fd, "compressed ply file");
     write_at(fd, reinterpret_cast<const uint8_t *>(head.data()), head.size(), base);
-    const std::vector<Region> rs = compressed_ply_regions(m, C, dchunk, dvert, dsh);
+    const std::vector<Region> rs = compressed_ply_regions(a);
     const uint64_t body = base + head.size();
     const uint64_t total = body + (rs.empty() ? 0 : rs.back().off + rs.back().bytes);
     FileRing ring(c, fd);
-    try {
-        bool ok = true;
-        for (size_t i = 0; i < rs.size() && ok; ++i)
-            for (uint64_t o = 0; o < rs[i].bytes && ok; o += ring.slot) {
-                const uint64_t nb = std::min(ring.slot, rs[i].bytes - o);
-                uint8_t *host = ring.next();
-                if (!(ok = host != nullptr)) break;
-                ST_HIP(hipMemcpyAsync(host, rs[i].dev + o, nb, hipMemcpyDeviceToHost, c->stream));
-                ring.submit(nb, body + rs[i].off + o);
-            }
-    } catch (...) {
-        ring.fail(std::current_exception());
-    }
+    for (const Region &r : rs) device_bytes_to_file(ring, r.dev, r.bytes, body + r.off);
     ring.finish();
     file_end(fd, total, "compressed ply file");
     return total - base;
@@ -420,38 +462,35 @@ uint64_t compressed_ply_to_file(st_ctx *c, uint64_t m, int C, const float *dchun
 // (slot / 4 * 3 stream bytes) encoded into one of two device staging buffers, then copied into the
 // slot while the writer thread writes the slot before.  A page without fetch(contentUrl) is written
 // alone.
-uint64_t html_to_file(st_ctx *c, const HtmlParts &page, uint64_t m, int C, const float *dchunk,
-                      const uint32_t *dvert, const uint8_t *dsh, int fd, const char *version) {
+uint64_t html_to_file(st_ctx *c, const HtmlParts &page, const CplyArrays &a, int fd, const char *version) {
     const uint64_t base = file_base(fd, "html file");
     write_at(fd, reinterpret_cast<const uint8_t *>(page.prefix.data()), page.prefix.size(), base);
     uint64_t total = base + page.prefix.size();
     if (page.embeds) {
-        const std::string head = compressed_ply_header(m, C, version);
+        const std::string head = compressed_ply_header(a.m, a.C, version);
         auto *dhead = wsT<uint8_t>(c, "htmlw.head", head.size());
         ST_HIP(hipMemcpyAsync(dhead, head.data(), head.size(), hipMemcpyHostToDevice, c->stream));
         ST_HIP(hipStreamSynchronize(c->stream));  // (head is pageable and leaves with this scope)
         std::vector<st_bytes_seg> segs{{dhead, head.size()}};
         uint64_t bytes = head.size();
-        for (const Region &r : compressed_ply_regions(m, C, dchunk, dvert, dsh)) {
+        for (const Region &r : compressed_ply_regions(a)) {
             segs.push_back({r.dev, r.bytes});
             bytes += r.bytes;
         }
         FileRing ring(c, fd);
         const uint64_t piece = ring.slot / 4 * 3;  // a multiple of 3: the slot is whole MiB
         uint8_t *stage[2] = {wsT<uint8_t>(c, "htmlw.stage0", ring.slot), wsT<uint8_t>(c, "htmlw.stage1", ring.slot)};
-        try {
-            int k = 0;
-            for (uint64_t b = 0; b < bytes; b += piece, ++k) {
-                const uint64_t nb = std::min(piece, bytes - b), nt = base64_size(nb);
-                uint8_t *host = ring.next();
-                if (!host) break;
+        uint64_t b = 0, nb = 0;  // the piece's first stream byte and its stream bytes
+        pump(
+            ring,
+            [&](uint64_t k) {
+                b = k * piece, nb = b < bytes ? std::min(piece, bytes - b) : 0;
+                return Part{base64_size(nb), total + b / 3 * 4};
+            },
+            [&](uint64_t k) {
                 base64_dev(c, segs.data(), (int)segs.size(), b, nb, stage[k & 1]);
-                ST_HIP(hipMemcpyAsync(host, stage[k & 1], nt, hipMemcpyDeviceToHost, c->stream));
-                ring.submit(nt, total + b / 3 * 4);
-            }
-        } catch (...) {
-            ring.fail(std::current_exception());
-        }
+                return stage[k & 1];
+            });
         ring.finish();
         total += base64_size(bytes);
         write_at(fd, reinterpret_cast<const uint8_t *>(page.suffix.data()), page.suffix.size(), total);
@@ -459,22 +498,6 @@ uint64_t html_to_file(st_ctx *c, const HtmlParts &page, uint64_t m, int C, const
     }
     file_end(fd, total, "html file");
     return total - base;
-}
-
-// the compressed-PLY arrays of the chain's table (workspace slots of st_compressed_ply_file), then
-// the page around their text
-void html_chain_to_file(Chain &ch, const HtmlParts &page, int fd, const char *version, uint64_t *out_m,
-                        int32_t *out_sh_coeffs, uint64_t *size) {
-    st_ctx *c = ch.c;
-    const uint64_t m = ch.n, nch = (m + 255) / 256;
-    auto *dchunk = wsT<float>(c, "chain.chunk", nch * 18);
-    auto *dvert = wsT<uint32_t>(c, "chain.vert", m * 4);
-    auto *dsh = wsT<uint8_t>(c, "chain.sh", m * 3 * (uint64_t)ch.coeffs() + 1);
-    int32_t C = 0;
-    compressed_tail(ch, dchunk, dvert, dsh, &C);
-    *size = html_to_file(c, page, m, C, dchunk, dvert, dsh, fd, version);
-    *out_m = m;
-    *out_sh_coeffs = C;
 }
 
 // writePly's rows (write-ply.ts:37-67) of a device table to fd at file offset `off`: rows are
@@ -488,31 +511,26 @@ uint64_t ply_rows_to_file(st_ctx *c, const st_ttable *t, int fd, uint64_t off) {
     const uint64_t per = (uint64_t)pr.RB * pr.R;  // <= 48 KiB
     const uint64_t piece_rows = std::max<uint64_t>(1, ring.slot / per) * pr.RB;
     uint8_t *stage[2] = {wsT<uint8_t>(c, "plyw.stage0", piece_rows * pr.R), wsT<uint8_t>(c, "plyw.stage1", piece_rows * pr.R)};
-    try {
-        int k = 0;
-        for (uint64_t row = 0; row < t->n; row += piece_rows, ++k) {
-            const uint64_t nr = std::min(piece_rows, t->n - row), nb = nr * pr.R;
-            uint8_t *host = ring.next();
-            if (!host) break;
+    uint64_t row = 0, nr = 0;
+    pump(
+        ring,
+        [&](uint64_t k) {
+            row = k * piece_rows, nr = row < t->n ? std::min(piece_rows, t->n - row) : 0;
+            return Part{nr * pr.R, off + row * pr.R};
+        },
+        [&](uint64_t k) {
             pr.run(row, nr, stage[k & 1]);
-            ST_HIP(hipMemcpyAsync(host, stage[k & 1], nb, hipMemcpyDeviceToHost, c->stream));
-            ring.submit(nb, off + row * pr.R);
-        }
-    } catch (...) {
-        ring.fail(std::current_exception());
-    }
+            return stage[k & 1];
+        });
     ring.finish();
     return t->n * pr.R;
 }
 
-// header + rows of the chain's table to out_fd from its position (writePly with one element named
-// "vertex", index.ts:126-133)
-uint64_t ply_chain_to_file(Chain &ch, const char *const *comments, int ncomments, int fd) {
-    const st_ttable *t = ch.typed();
-    const std::string head = ply_header_text(t, "vertex", comments, ncomments, false);
+// `head` (a header, or nothing: an element's rows alone) + the table's rows to fd from its position
+uint64_t ply_table_to_file(st_ctx *c, const std::string &head, const st_ttable *t, int fd) {
     const uint64_t base = file_base(fd, "ply file");
     write_at(fd, reinterpret_cast<const uint8_t *>(head.data()), head.size(), base);
-    const uint64_t total = base + head.size() + ply_rows_to_file(ch.c, t, fd, base + head.size());
+    const uint64_t total = base + head.size() + ply_rows_to_file(c, t, fd, base + head.size());
     file_end(fd, total, "ply file");
     return total - base;
 }
@@ -528,24 +546,23 @@ uint64_t csv_rows_to_file(st_ctx *c, CsvRows &cr, const st_ttable *t, int fd, ui
     const uint64_t piece_rows = cr.piece_rows(std::min<uint64_t>(ring.slot, CSV_PIECE_BYTES));
     const uint64_t stage_bytes = piece_rows * cr.W + 8;
     uint8_t *stage[2] = {wsT<uint8_t>(c, "csvw.stage0", stage_bytes), wsT<uint8_t>(c, "csvw.stage1", stage_bytes)};
-    uint64_t done = 0;
-    try {
-        int k = 0;
-        for (uint64_t row = 0; row < t->n; row += piece_rows, ++k) {
-            const uint64_t nr = std::min(piece_rows, t->n - row);
-            const uint64_t nb = cr.measure(row, nr);
-            uint8_t *host = ring.next();
-            if (!host) break;
+    uint64_t row = 0, nr = 0, next = off;  // the piece's rows; the file offset after the pieces measured so far
+    pump(
+        ring,
+        [&](uint64_t k) {
+            row = k * piece_rows;
+            if (row >= t->n) return Part{0, next};
+            nr = std::min(piece_rows, t->n - row);
+            const Part p{cr.measure(row, nr), next};
+            next += p.bytes;
+            return p;
+        },
+        [&](uint64_t k) {
             cr.write(row, nr, stage[k & 1], 0);
-            ST_HIP(hipMemcpyAsync(host, stage[k & 1], nb, hipMemcpyDeviceToHost, c->stream));
-            ring.submit(nb, off + done);
-            done += nb;
-        }
-    } catch (...) {
-        ring.fail(std::current_exception());
-    }
+            return stage[k & 1];
+        });
     ring.finish();
-    return done;
+    return next - off;
 }
 
 // header + rows of a device table to out_fd from its position (writeCsv, index.ts:117-118)
@@ -570,30 +587,37 @@ uint64_t splat_table_to_file(st_ctx *c, const st_ttable *t, int fd) {
         FileRing ring(c, fd);
         const uint64_t piece_rows = std::max<uint64_t>(1, ring.slot / 32);
         uint8_t *stage[2] = {wsT<uint8_t>(c, "splatw.stage0", piece_rows * 32), wsT<uint8_t>(c, "splatw.stage1", piece_rows * 32)};
-        try {
-            int k = 0;
-            for (uint64_t row = 0; row < W.n; row += piece_rows, ++k) {
-                const uint64_t nr = std::min(piece_rows, W.n - row), nb = nr * 32;
-                uint8_t *host = ring.next();
-                if (!host) break;
+        uint64_t row = 0, nr = 0;
+        pump(
+            ring,
+            [&](uint64_t k) {
+                row = k * piece_rows, nr = row < W.n ? std::min(piece_rows, W.n - row) : 0;
+                return Part{nr * 32, base + row * 32};
+            },
+            [&](uint64_t k) {
                 splat_rows_dev(c, W, row, nr, stage[k & 1]);
-                ST_HIP(hipMemcpyAsync(host, stage[k & 1], nb, hipMemcpyDeviceToHost, c->stream));
-                ring.submit(nb, base + row * 32);
-            }
-        } catch (...) {
-            ring.fail(std::current_exception());
-        }
+                return stage[k & 1];
+            });
         ring.finish();
     }
     file_end(fd, base + W.n * 32, "splat file");
     return W.n * 32;
 }
 
+// an image that lies whole in HBM to fd from `base`, the position it was found at
+void image_to_file(st_ctx *c, const uint8_t *image, uint64_t size, int fd, uint64_t base, const char *what) {
+    {
+        FileRing ring(c, fd);
+        device_bytes_to_file(ring, image, size, base);
+        ring.finish();
+    }
+    file_end(fd, base + size, what);
+}
+
 // the raw .spz image (header + six planes) of a device table to fd from its position: built whole
 // in HBM -- it is smaller than the table it comes from -- and copied down through the ring.  gz: the
 // gzip member around the image (st_deflate.hip), made in HBM beside it, is what goes down
-uint64_t spz_table_to_file(st_ctx *c, const st_ttable *t, int fractional_bits, int fd, uint64_t *clamped,
-                           bool gz = false) {
+uint64_t spz_table_to_file(st_ctx *c, const st_ttable *t, int fractional_bits, int fd, uint64_t *clamped, bool gz) {
     const WrTable W = wr_table(t, true, "spz file");
     spz_check(W, fractional_bits);
     const uint64_t base = file_base(fd, "spz file");
@@ -606,22 +630,7 @@ uint64_t spz_table_to_file(st_ctx *c, const st_ttable *t, int fractional_bits, i
         size = gzip_dev(c, image, size, member, cap);
         image = member;
     }
-    {
-        FileRing ring(c, fd);
-        try {
-            for (uint64_t o = 0; o < size; o += ring.slot) {
-                const uint64_t nb = std::min(ring.slot, size - o);
-                uint8_t *host = ring.next();
-                if (!host) break;
-                ST_HIP(hipMemcpyAsync(host, image + o, nb, hipMemcpyDeviceToHost, c->stream));
-                ring.submit(nb, base + o);
-            }
-        } catch (...) {
-            ring.fail(std::current_exception());
-        }
-        ring.finish();
-    }
-    file_end(fd, base + size, "spz file");
+    image_to_file(c, image, size, fd, base, "spz file");
     return size;
 }
 
@@ -637,46 +646,202 @@ uint64_t ksplat_table_to_file(st_ctx *c, const st_ttable *t, int mode, int degre
     const uint64_t size = ksplat_plan_image_size(K, P);
     auto *image = wsT<uint8_t>(c, "ksw.image", size);
     ksplat_image_from_plan(c, W, P, K, image);
-    {
-        FileRing ring(c, fd);
-        try {
-            for (uint64_t o = 0; o < size; o += ring.slot) {
-                const uint64_t nb = std::min(ring.slot, size - o);
-                uint8_t *host = ring.next();
-                if (!host) break;
-                ST_HIP(hipMemcpyAsync(host, image + o, nb, hipMemcpyDeviceToHost, c->stream));
-                ring.submit(nb, base + o);
-            }
-        } catch (...) {
-            ring.fail(std::current_exception());
-        }
-        ring.finish();
-    }
-    file_end(fd, base + size, "ksplat file");
+    image_to_file(c, image, size, fd, base, "ksplat file");
     return size;
 }
 
-// the host table into the chain
-auto host_loader(st_ctx *c, const st_ttable *src) {
-    return [=](Chain &ch) {
-        ST_ARG(c && src, "NULL argument");
-        check_src(src);
-        upload_chain(c, src, ch);
-    };
+// ---- where a one-call form's table comes from -----------------------------------------------
+// ok(): the source's own arguments are there (else "NULL argument"); check(): the table's errors
+// that need no device; load(): the table into the chain's device columns; table(): the processed
+// table as a writer takes it.
+
+// a host table, uploaded once
+struct HostSrc {
+    const st_ttable *t;
+    bool ok() const { return t; }
+    void check() const { check_src(t); }
+    void load(Chain &ch) const { upload_chain(ch.c, t, ch); }
+    const st_ttable *table(Chain &ch) const { return ch.typed(); }
+};
+
+// an element of a .ply file behind a descriptor, read straight into HBM
+struct PlySrc {
+    int32_t fd;
+    const st_ply_header *h;
+    int32_t element;
+    bool ok() const { return h && fd >= 0; }
+    void check() const {}
+    void load(Chain &ch) const { ply_chain(ch.c, fd, h, element, ch); }
+    const st_ttable *table(Chain &ch) const { return ch.typed(); }
+};
+
+// a table already in HBM.  Its forms take no actions and the writer gets the caller's st_ttable as
+// it is: a column name may be NULL there (check_src and wr_table allow it), which a ChainCol's
+// std::string cannot hold, so the chain learns the row count alone
+struct DevSrc {
+    const st_ttable *t;
+    bool ok() const { return t; }
+    void check() const { check_src(t); }
+    void load(Chain &ch) const { ch.n = t->n; }
+    const st_ttable *table(Chain &) const { return t; }
+};
+
+// a one-call file form: the source's table, the actions, the format's writer into out_fd.  A
+// caller sees the checks in this order: NULL arguments, the format's parameters (`pre`), the
+// source table, the output descriptor; the device comes after all of them.  write(chain, table)
+// returns the bytes written.  (A device form has no row count to report: it passes a local.)
+template <typename Src, typename Pre, typename Write>
+void file_form(st_ctx *c, const Src &src, const st_action *actions, int32_t nactions, int32_t out_fd, uint64_t *out_m,
+               uint64_t *size, Pre pre, Write write) {
+    ST_REQUIRE(c && src.ok() && out_m && size && (actions || nactions == 0), ST_ERR_ARG, "NULL argument");
+    pre();
+    src.check();
+    sog_file_check(out_fd);
+    use_device(c);
+    Chain ch{c};
+    src.load(ch);
+    run_actions(ch, actions, nactions);
+    *size = write(ch, src.table(ch));
+    *out_m = ch.n;
 }
 
-// processDataTable + writeSog on a table the loader puts in the chain, into the sink.  One device
-// takes every column type (sog_tdev); with the st_set_devices group the processed float32 columns
-// are sharded over it from the host.
-template <typename Load>
-void sog_chain(st_ctx *c, Load load, const st_action *actions, int32_t nactions, int32_t iters, const double *draws,
-               uint64_t ndraws, uint64_t *used, const SogSink &to) {
+// the forms of each format: its parameter checks and its writer around file_form
+template <typename Src>
+int html_form(st_ctx *c, const Src &src, const st_action *actions, int32_t nactions, const char *html, const char *css,
+              const char *js, const double *camera, const double *target, int32_t out_fd, const char *version,
+              uint64_t *out_m, int32_t *out_sh_coeffs, uint64_t *size) {
+    return guard([&] {
+        HtmlParts page;
+        file_form(
+            c, src, actions, nactions, out_fd, out_m, size,
+            [&] {
+                ST_REQUIRE(out_sh_coeffs, ST_ERR_ARG, "NULL argument");
+                page = html_parts(html, css, js, camera, target);
+            },
+            [&](Chain &ch, const st_ttable *) {
+                const CplyArrays a = compressed_arrays(ch);
+                const uint64_t bytes = html_to_file(c, page, a, out_fd, version);
+                *out_sh_coeffs = a.C;
+                return bytes;
+            });
+    });
+}
+
+// the rows alone (no header, no actions)
+template <typename Src>
+int ply_rows_form(st_ctx *c, const Src &src, int32_t out_fd, uint64_t *size) {
+    return guard([&] {
+        uint64_t rows;
+        file_form(c, src, nullptr, 0, out_fd, &rows, size, [] {},
+                  [&](Chain &, const st_ttable *t) { return ply_table_to_file(c, "", t, out_fd); });
+    });
+}
+
+// writePly with one element named "vertex" (index.ts:126-133)
+template <typename Src>
+int ply_form(st_ctx *c, const Src &src, const st_action *actions, int32_t nactions, const char *const *comments,
+             int32_t ncomments, int32_t out_fd, uint64_t *out_m, uint64_t *size) {
+    return guard([&] {
+        file_form(
+            c, src, actions, nactions, out_fd, out_m, size,
+            [&] { ST_REQUIRE(ncomments >= 0 && (comments || ncomments == 0), ST_ERR_ARG, "ply file: NULL comments"); },
+            [&](Chain &, const st_ttable *t) {
+                return ply_table_to_file(c, ply_header_text(t, "vertex", comments, ncomments, false), t, out_fd);
+            });
+    });
+}
+
+template <typename Src>
+int csv_form(st_ctx *c, const Src &src, const st_action *actions, int32_t nactions, int32_t out_fd, uint64_t *out_m,
+             uint64_t *size) {
+    return guard([&] {
+        file_form(c, src, actions, nactions, out_fd, out_m, size, [] {},
+                  [&](Chain &, const st_ttable *t) { return csv_table_to_file(c, t, out_fd); });
+    });
+}
+
+template <typename Src>
+int splat_form(st_ctx *c, const Src &src, const st_action *actions, int32_t nactions, int32_t out_fd, uint64_t *out_m,
+               uint64_t *size) {
+    return guard([&] {
+        file_form(c, src, actions, nactions, out_fd, out_m, size, [] {},
+                  [&](Chain &, const st_ttable *t) { return splat_table_to_file(c, t, out_fd); });
+    });
+}
+
+// gz: the gzip member around the image, deflated on the device
+template <typename Src>
+int spz_form(st_ctx *c, const Src &src, const st_action *actions, int32_t nactions, int32_t fractional_bits,
+             int32_t out_fd, uint64_t *out_m, uint64_t *size, uint64_t *out_clamped, bool gz) {
+    return guard([&] {
+        file_form(
+            c, src, actions, nactions, out_fd, out_m, size,
+            [&] {
+                ST_REQUIRE(fractional_bits >= 0 && fractional_bits <= 23, ST_ERR_ARG, "spz: fractional_bits must be 0..23");
+            },
+            [&](Chain &, const st_ttable *t) { return spz_table_to_file(c, t, fractional_bits, out_fd, out_clamped, gz); });
+    });
+}
+
+template <typename Src>
+int ksplat_form(st_ctx *c, const Src &src, const st_action *actions, int32_t nactions, int32_t mode, int32_t degree,
+                float block_size, float sh_min, float sh_max, int32_t out_fd, uint64_t *out_m, uint64_t *size,
+                uint64_t *out_clamped) {
+    return guard([&] {
+        file_form(
+            c, src, actions, nactions, out_fd, out_m, size,
+            [&] {  // the parameter checks that need no table (the table's own follow in ksplat_params)
+                ST_REQUIRE(mode >= 0 && mode <= 2, ST_ERR_ARG, "ksplat: mode must be 0, 1 or 2");
+                ST_REQUIRE(degree >= -1 && degree <= 3, ST_ERR_ARG, "ksplat: degree must be -1..3");
+                ST_REQUIRE(block_size > 0.0f && block_size < __builtin_inff(), ST_ERR_ARG,
+                           "ksplat: block_size must be finite and > 0 as a float32");
+            },
+            [&](Chain &, const st_ttable *t) {
+                return ksplat_table_to_file(c, t, mode, degree, block_size, sh_min, sh_max, out_fd, out_clamped);
+            });
+    });
+}
+
+// processDataTable + writeCompressedPly's arrays into the caller's host arrays
+template <typename Src>
+int compressed_ply_arrays_form(st_ctx *c, const Src &src, const st_action *actions, int32_t nactions, float *chunk,
+                               uint32_t *vertex, uint8_t *sh, uint64_t *out_m, int32_t *out_sh_coeffs) {
+    return guard([&] {
+        ST_REQUIRE(c && src.ok() && out_m && out_sh_coeffs && (actions || nactions == 0), ST_ERR_ARG, "NULL argument");
+        src.check();
+        use_device(c);
+        Chain ch{c};
+        src.load(ch);
+        run_actions(ch, actions, nactions);
+        ST_REQUIRE(ch.n == 0 || (chunk && vertex), ST_ERR_ARG, "compressed_ply: NULL output");
+        const CplyArrays a = compressed_arrays(ch);
+        ST_REQUIRE(a.C == 0 || a.m == 0 || sh, ST_ERR_ARG, "compressed_ply: sh output is NULL");
+        std::vector<HostXfer> down;
+        if (a.m) {
+            down.push_back(HostXfer{chunk, a.chunk, (a.m + 255) / 256 * 72});
+            down.push_back(HostXfer{vertex, a.vert, a.m * 16});
+            if (a.C) down.push_back(HostXfer{sh, a.sh, a.m * 3 * (uint64_t)a.C});
+        }
+        staged_d2h(c, down);
+        *out_m = a.m;
+        *out_sh_coeffs = a.C;
+    });
+}
+
+// processDataTable + writeSog on the source's table, into the sink.  One device takes every
+// column type (sog_tdev); with the st_set_devices group the processed float32 columns are
+// sharded over it from the host.
+template <typename Src>
+void sog_chain(st_ctx *c, const Src &src, const st_action *actions, int32_t nactions, int32_t iters,
+               const double *draws, uint64_t ndraws, uint64_t *used, const SogSink &to) {
     const auto group = sog_group();  // held for the whole call
     ST_ARG(c && to.ok(), "NULL argument");
     ST_ARG(actions || nactions == 0, "NULL argument");
     use_device(c);
+    ST_ARG(src.ok(), "NULL argument");
+    src.check();
     Chain ch{c};
-    load(ch);
+    src.load(ch);
     run_actions(ch, actions, nactions);
     if (group) {
         const st_table *t = sog_view(ch);
@@ -729,11 +894,12 @@ extern "C" {
 int st_process(st_ctx *c, const st_ttable *src, const st_action *actions, int32_t nactions, const st_ttable *dst,
                uint64_t *out_m) {
     return guard([&] {
-        ST_REQUIRE(c && src && dst && out_m && (actions || nactions == 0), ST_ERR_ARG, "NULL argument");
-        check_src(src);
+        const HostSrc host{src};
+        ST_REQUIRE(c && host.ok() && dst && out_m && (actions || nactions == 0), ST_ERR_ARG, "NULL argument");
+        host.check();
         use_device(c);
         Chain ch{c};
-        upload_chain(c, src, ch);
+        host.load(ch);
         run_actions(ch, actions, nactions);
         std::vector<int> from(dst->ncol, -1);
         for (int j = 0; j < dst->ncol; ++j) {
@@ -751,32 +917,7 @@ int st_process(st_ctx *c, const st_ttable *src, const st_action *actions, int32_
 
 int st_compressed_ply(st_ctx *c, const st_ttable *src, const st_action *actions, int32_t nactions, float *chunk,
                       uint32_t *vertex, uint8_t *sh, uint64_t *out_m, int32_t *out_sh_coeffs) {
-    return guard([&] {
-        ST_REQUIRE(c && src && out_m && out_sh_coeffs && (actions || nactions == 0), ST_ERR_ARG, "NULL argument");
-        check_src(src);
-        use_device(c);
-        Chain ch{c};
-        upload_chain(c, src, ch);
-        run_actions(ch, actions, nactions);
-        const uint64_t m = ch.n, nch = (m + 255) / 256;
-        ST_REQUIRE(m == 0 || (chunk && vertex), ST_ERR_ARG, "compressed_ply: NULL output");
-        auto *dchunk = wsT<float>(c, "chain.chunk", nch * 18);
-        auto *dvert = wsT<uint32_t>(c, "chain.vert", m * 4);
-        const int Cmax = ch.coeffs();
-        auto *dsh = wsT<uint8_t>(c, "chain.sh", m * 3 * (uint64_t)Cmax + 1);
-        int32_t C = 0;
-        compressed_tail(ch, dchunk, dvert, dsh, &C);
-        ST_REQUIRE(C == 0 || m == 0 || sh, ST_ERR_ARG, "compressed_ply: sh output is NULL");
-        std::vector<HostXfer> down;
-        if (m) {
-            down.push_back(HostXfer{chunk, dchunk, nch * 18 * 4});
-            down.push_back(HostXfer{vertex, dvert, m * 16});
-            if (C) down.push_back(HostXfer{sh, dsh, m * 3 * (uint64_t)C});
-        }
-        staged_d2h(c, down);
-        *out_m = m;
-        *out_sh_coeffs = C;
-    });
+    return compressed_ply_arrays_form(c, HostSrc{src}, actions, nactions, chunk, vertex, sh, out_m, out_sh_coeffs);
 }
 
 int st_dev_compressed_ply(st_ctx *c, const st_ttable *src, const st_action *actions, int32_t nactions,
@@ -801,65 +942,40 @@ int st_dev_compressed_ply(st_ctx *c, const st_ttable *src, const st_action *acti
 int st_ply_compressed_ply(st_ctx *c, int32_t fd, const st_ply_header *h, int32_t element, const st_action *actions,
                           int32_t nactions, float *chunk, uint32_t *vertex, uint8_t *sh, uint64_t *out_m,
                           int32_t *out_sh_coeffs) {
-    return guard([&] {
-        ST_REQUIRE(c && h && fd >= 0 && out_m && out_sh_coeffs && (actions || nactions == 0), ST_ERR_ARG,
-                   "NULL argument");
-        use_device(c);
-        Chain ch{c};
-        ply_chain(c, fd, h, element, ch);
-        run_actions(ch, actions, nactions);
-        const uint64_t m = ch.n, nch = (m + 255) / 256;
-        ST_REQUIRE(m == 0 || (chunk && vertex), ST_ERR_ARG, "compressed_ply: NULL output");
-        auto *dchunk = wsT<float>(c, "chain.chunk", nch * 18);
-        auto *dvert = wsT<uint32_t>(c, "chain.vert", m * 4);
-        auto *dsh = wsT<uint8_t>(c, "chain.sh", m * 3 * (uint64_t)ch.coeffs() + 1);
-        int32_t C = 0;
-        compressed_tail(ch, dchunk, dvert, dsh, &C);
-        ST_REQUIRE(C == 0 || m == 0 || sh, ST_ERR_ARG, "compressed_ply: sh output is NULL");
-        std::vector<HostXfer> down;
-        if (m) {
-            down.push_back(HostXfer{chunk, dchunk, nch * 18 * 4});
-            down.push_back(HostXfer{vertex, dvert, m * 16});
-            if (C) down.push_back(HostXfer{sh, dsh, m * 3 * (uint64_t)C});
-        }
-        staged_d2h(c, down);
-        *out_m = m;
-        *out_sh_coeffs = C;
-    });
+    return compressed_ply_arrays_form(c, PlySrc{fd, h, element}, actions, nactions, chunk, vertex, sh, out_m,
+                                      out_sh_coeffs);
 }
 
+// file_form's steps longhand: ST_DEBUG's stamps want the stream drained after the ingest and after
+// the arrays are made, which no other form does
 int st_ply_compressed_ply_file(st_ctx *c, int32_t fd, const st_ply_header *h, int32_t element,
                                const st_action *actions, int32_t nactions, int32_t out_fd, const char *version,
                                uint64_t *out_m, int32_t *out_sh_coeffs, uint64_t *size) {
     return guard([&] {
-        ST_REQUIRE(c && h && fd >= 0 && out_m && out_sh_coeffs && size && (actions || nactions == 0), ST_ERR_ARG,
+        const PlySrc ply{fd, h, element};
+        ST_REQUIRE(c && ply.ok() && out_m && out_sh_coeffs && size && (actions || nactions == 0), ST_ERR_ARG,
                    "NULL argument");
         sog_file_check(out_fd);
         use_device(c);
         using clk = std::chrono::steady_clock;
         const auto t0 = clk::now();
         Chain ch{c};
-        ply_chain(c, fd, h, element, ch);
+        ply.load(ch);
         ST_HIP(hipStreamSynchronize(c->stream));  // (ST_DEBUG's stamps: the ingest alone)
         const auto t1 = clk::now();
         run_actions(ch, actions, nactions);
-        const uint64_t m = ch.n, nch = (m + 255) / 256;
-        auto *dchunk = wsT<float>(c, "chain.chunk", nch * 18);
-        auto *dvert = wsT<uint32_t>(c, "chain.vert", m * 4);
-        auto *dsh = wsT<uint8_t>(c, "chain.sh", m * 3 * (uint64_t)ch.coeffs() + 1);
-        int32_t C = 0;
-        compressed_tail(ch, dchunk, dvert, dsh, &C);
+        const CplyArrays a = compressed_arrays(ch);
         ST_HIP(hipStreamSynchronize(c->stream));
         const auto t2 = clk::now();
-        *size = compressed_ply_to_file(c, m, C, dchunk, dvert, dsh, out_fd, version);
-        *out_m = m;
-        *out_sh_coeffs = C;
+        *size = compressed_ply_to_file(c, a, out_fd, version);
+        *out_m = a.m;
+        *out_sh_coeffs = a.C;
         if (std::getenv("ST_DEBUG")) {
-            const auto ms = [](clk::time_point a, clk::time_point b) {
-                return std::chrono::duration<double, std::milli>(b - a).count();
+            const auto ms = [](clk::time_point from, clk::time_point to) {
+                return std::chrono::duration<double, std::milli>(to - from).count();
             };
             fprintf(stderr, "[st cply file] ingest %.1f ms, chain %.1f ms, file %.1f ms (%llu rows)\n", ms(t0, t1),
-                    ms(t1, t2), ms(t2, clk::now()), (unsigned long long)m);
+                    ms(t1, t2), ms(t2, clk::now()), (unsigned long long)a.m);
         }
     });
 }
@@ -867,348 +983,146 @@ int st_ply_compressed_ply_file(st_ctx *c, int32_t fd, const st_ply_header *h, in
 int st_compressed_ply_file(st_ctx *c, const st_ttable *src, const st_action *actions, int32_t nactions, int32_t out_fd,
                            const char *version, uint64_t *out_m, int32_t *out_sh_coeffs, uint64_t *size) {
     return guard([&] {
-        ST_REQUIRE(c && src && out_m && out_sh_coeffs && size && (actions || nactions == 0), ST_ERR_ARG,
-                   "NULL argument");
-        check_src(src);
-        sog_file_check(out_fd);
-        use_device(c);
-        Chain ch{c};
-        upload_chain(c, src, ch);
-        run_actions(ch, actions, nactions);
-        const uint64_t m = ch.n, nch = (m + 255) / 256;
-        auto *dchunk = wsT<float>(c, "chain.chunk", nch * 18);
-        auto *dvert = wsT<uint32_t>(c, "chain.vert", m * 4);
-        auto *dsh = wsT<uint8_t>(c, "chain.sh", m * 3 * (uint64_t)ch.coeffs() + 1);
-        int32_t C = 0;
-        compressed_tail(ch, dchunk, dvert, dsh, &C);
-        *size = compressed_ply_to_file(c, m, C, dchunk, dvert, dsh, out_fd, version);
-        *out_m = m;
-        *out_sh_coeffs = C;
+        file_form(
+            c, HostSrc{src}, actions, nactions, out_fd, out_m, size,
+            [&] { ST_REQUIRE(out_sh_coeffs, ST_ERR_ARG, "NULL argument"); },
+            [&](Chain &ch, const st_ttable *) {
+                const CplyArrays a = compressed_arrays(ch);
+                const uint64_t bytes = compressed_ply_to_file(c, a, out_fd, version);
+                *out_sh_coeffs = a.C;
+                return bytes;
+            });
     });
 }
 
 int st_html_file(st_ctx *c, const st_ttable *src, const st_action *actions, int32_t nactions, const char *html,
                  const char *css, const char *js, const double *camera, const double *target, int32_t out_fd,
                  const char *version, uint64_t *out_m, int32_t *out_sh_coeffs, uint64_t *size) {
-    return guard([&] {
-        ST_REQUIRE(c && src && out_m && out_sh_coeffs && size && (actions || nactions == 0), ST_ERR_ARG,
-                   "NULL argument");
-        const HtmlParts page = html_parts(html, css, js, camera, target);
-        check_src(src);
-        sog_file_check(out_fd);
-        use_device(c);
-        Chain ch{c};
-        upload_chain(c, src, ch);
-        run_actions(ch, actions, nactions);
-        html_chain_to_file(ch, page, out_fd, version, out_m, out_sh_coeffs, size);
-    });
+    return html_form(c, HostSrc{src}, actions, nactions, html, css, js, camera, target, out_fd, version, out_m,
+                     out_sh_coeffs, size);
 }
 
 int st_ply_html_file(st_ctx *c, int32_t fd, const st_ply_header *h, int32_t element, const st_action *actions,
                      int32_t nactions, const char *html, const char *css, const char *js, const double *camera,
                      const double *target, int32_t out_fd, const char *version, uint64_t *out_m,
                      int32_t *out_sh_coeffs, uint64_t *size) {
-    return guard([&] {
-        ST_REQUIRE(c && h && fd >= 0 && out_m && out_sh_coeffs && size && (actions || nactions == 0), ST_ERR_ARG,
-                   "NULL argument");
-        const HtmlParts page = html_parts(html, css, js, camera, target);
-        sog_file_check(out_fd);
-        use_device(c);
-        Chain ch{c};
-        ply_chain(c, fd, h, element, ch);
-        run_actions(ch, actions, nactions);
-        html_chain_to_file(ch, page, out_fd, version, out_m, out_sh_coeffs, size);
-    });
+    return html_form(c, PlySrc{fd, h, element}, actions, nactions, html, css, js, camera, target, out_fd, version,
+                     out_m, out_sh_coeffs, size);
 }
 
 int st_dev_ply_rows_file(st_ctx *c, const st_ttable *t, int32_t out_fd, uint64_t *size) {
-    return guard([&] {
-        ST_REQUIRE(c && t && size, ST_ERR_ARG, "NULL argument");
-        check_src(t);
-        sog_file_check(out_fd);
-        use_device(c);
-        const uint64_t base = file_base(out_fd, "ply file");
-        *size = ply_rows_to_file(c, t, out_fd, base);
-        file_end(out_fd, base + *size, "ply file");
-    });
+    return ply_rows_form(c, DevSrc{t}, out_fd, size);
 }
 
 int st_ply_rows_file(st_ctx *c, const st_ttable *src, int32_t out_fd, uint64_t *size) {
-    return guard([&] {
-        ST_REQUIRE(c && src && size, ST_ERR_ARG, "NULL argument");
-        check_src(src);
-        sog_file_check(out_fd);
-        use_device(c);
-        Chain ch{c};
-        upload_chain(c, src, ch);
-        const uint64_t base = file_base(out_fd, "ply file");
-        *size = ply_rows_to_file(c, ch.typed(), out_fd, base);
-        file_end(out_fd, base + *size, "ply file");
-    });
+    return ply_rows_form(c, HostSrc{src}, out_fd, size);
 }
 
 int st_ply_file(st_ctx *c, const st_ttable *src, const st_action *actions, int32_t nactions,
                 const char *const *comments, int32_t ncomments, int32_t out_fd, uint64_t *out_m, uint64_t *size) {
-    return guard([&] {
-        ST_REQUIRE(c && src && out_m && size && (actions || nactions == 0), ST_ERR_ARG, "NULL argument");
-        ST_REQUIRE(ncomments >= 0 && (comments || ncomments == 0), ST_ERR_ARG, "ply file: NULL comments");
-        check_src(src);
-        sog_file_check(out_fd);
-        use_device(c);
-        Chain ch{c};
-        upload_chain(c, src, ch);
-        run_actions(ch, actions, nactions);
-        *size = ply_chain_to_file(ch, comments, ncomments, out_fd);
-        *out_m = ch.n;
-    });
+    return ply_form(c, HostSrc{src}, actions, nactions, comments, ncomments, out_fd, out_m, size);
 }
 
 int st_ply_ply_file(st_ctx *c, int32_t fd, const st_ply_header *h, int32_t element, const st_action *actions,
                     int32_t nactions, const char *const *comments, int32_t ncomments, int32_t out_fd,
                     uint64_t *out_m, uint64_t *size) {
-    return guard([&] {
-        ST_REQUIRE(c && h && fd >= 0 && out_m && size && (actions || nactions == 0), ST_ERR_ARG, "NULL argument");
-        ST_REQUIRE(ncomments >= 0 && (comments || ncomments == 0), ST_ERR_ARG, "ply file: NULL comments");
-        sog_file_check(out_fd);
-        use_device(c);
-        Chain ch{c};
-        ply_chain(c, fd, h, element, ch);
-        run_actions(ch, actions, nactions);
-        *size = ply_chain_to_file(ch, comments, ncomments, out_fd);
-        *out_m = ch.n;
-    });
+    return ply_form(c, PlySrc{fd, h, element}, actions, nactions, comments, ncomments, out_fd, out_m, size);
 }
 
 int st_dev_csv_file(st_ctx *c, const st_ttable *t, int32_t out_fd, uint64_t *size) {
-    return guard([&] {
-        ST_REQUIRE(c && t && size, ST_ERR_ARG, "NULL argument");
-        check_src(t);
-        sog_file_check(out_fd);
-        use_device(c);
-        *size = csv_table_to_file(c, t, out_fd);
-    });
+    uint64_t rows;
+    return csv_form(c, DevSrc{t}, nullptr, 0, out_fd, &rows, size);
 }
 
 int st_csv_file(st_ctx *c, const st_ttable *src, const st_action *actions, int32_t nactions, int32_t out_fd,
                 uint64_t *out_m, uint64_t *size) {
-    return guard([&] {
-        ST_REQUIRE(c && src && out_m && size && (actions || nactions == 0), ST_ERR_ARG, "NULL argument");
-        check_src(src);
-        sog_file_check(out_fd);
-        use_device(c);
-        Chain ch{c};
-        upload_chain(c, src, ch);
-        run_actions(ch, actions, nactions);
-        *size = csv_table_to_file(c, ch.typed(), out_fd);
-        *out_m = ch.n;
-    });
+    return csv_form(c, HostSrc{src}, actions, nactions, out_fd, out_m, size);
 }
 
 int st_ply_csv_file(st_ctx *c, int32_t fd, const st_ply_header *h, int32_t element, const st_action *actions,
                     int32_t nactions, int32_t out_fd, uint64_t *out_m, uint64_t *size) {
-    return guard([&] {
-        ST_REQUIRE(c && h && fd >= 0 && out_m && size && (actions || nactions == 0), ST_ERR_ARG, "NULL argument");
-        sog_file_check(out_fd);
-        use_device(c);
-        Chain ch{c};
-        ply_chain(c, fd, h, element, ch);
-        run_actions(ch, actions, nactions);
-        *size = csv_table_to_file(c, ch.typed(), out_fd);
-        *out_m = ch.n;
-    });
+    return csv_form(c, PlySrc{fd, h, element}, actions, nactions, out_fd, out_m, size);
 }
 
 int st_dev_splat_file(st_ctx *c, const st_ttable *t, int32_t out_fd, uint64_t *size) {
-    return guard([&] {
-        ST_REQUIRE(c && t && size, ST_ERR_ARG, "NULL argument");
-        check_src(t);
-        sog_file_check(out_fd);
-        use_device(c);
-        *size = splat_table_to_file(c, t, out_fd);
-    });
+    uint64_t rows;
+    return splat_form(c, DevSrc{t}, nullptr, 0, out_fd, &rows, size);
 }
 
 int st_splat_file(st_ctx *c, const st_ttable *src, const st_action *actions, int32_t nactions, int32_t out_fd,
                   uint64_t *out_m, uint64_t *size) {
-    return guard([&] {
-        ST_REQUIRE(c && src && out_m && size && (actions || nactions == 0), ST_ERR_ARG, "NULL argument");
-        check_src(src);
-        sog_file_check(out_fd);
-        use_device(c);
-        Chain ch{c};
-        upload_chain(c, src, ch);
-        run_actions(ch, actions, nactions);
-        *size = splat_table_to_file(c, ch.typed(), out_fd);
-        *out_m = ch.n;
-    });
+    return splat_form(c, HostSrc{src}, actions, nactions, out_fd, out_m, size);
 }
 
 int st_ply_splat_file(st_ctx *c, int32_t fd, const st_ply_header *h, int32_t element, const st_action *actions,
                       int32_t nactions, int32_t out_fd, uint64_t *out_m, uint64_t *size) {
-    return guard([&] {
-        ST_REQUIRE(c && h && fd >= 0 && out_m && size && (actions || nactions == 0), ST_ERR_ARG, "NULL argument");
-        sog_file_check(out_fd);
-        use_device(c);
-        Chain ch{c};
-        ply_chain(c, fd, h, element, ch);
-        run_actions(ch, actions, nactions);
-        *size = splat_table_to_file(c, ch.typed(), out_fd);
-        *out_m = ch.n;
-    });
+    return splat_form(c, PlySrc{fd, h, element}, actions, nactions, out_fd, out_m, size);
 }
 
 int st_dev_spz_file(st_ctx *c, const st_ttable *t, int32_t fractional_bits, int32_t out_fd, uint64_t *size,
                     uint64_t *out_clamped) {
-    return guard([&] {
-        ST_REQUIRE(c && t && size, ST_ERR_ARG, "NULL argument");
-        ST_REQUIRE(fractional_bits >= 0 && fractional_bits <= 23, ST_ERR_ARG, "spz: fractional_bits must be 0..23");
-        check_src(t);
-        sog_file_check(out_fd);
-        use_device(c);
-        *size = spz_table_to_file(c, t, fractional_bits, out_fd, out_clamped);
-    });
+    uint64_t rows;
+    return spz_form(c, DevSrc{t}, nullptr, 0, fractional_bits, out_fd, &rows, size, out_clamped, false);
 }
 
 int st_spz_file(st_ctx *c, const st_ttable *src, const st_action *actions, int32_t nactions, int32_t fractional_bits,
                 int32_t out_fd, uint64_t *out_m, uint64_t *size, uint64_t *out_clamped) {
-    return guard([&] {
-        ST_REQUIRE(c && src && out_m && size && (actions || nactions == 0), ST_ERR_ARG, "NULL argument");
-        ST_REQUIRE(fractional_bits >= 0 && fractional_bits <= 23, ST_ERR_ARG, "spz: fractional_bits must be 0..23");
-        check_src(src);
-        sog_file_check(out_fd);
-        use_device(c);
-        Chain ch{c};
-        upload_chain(c, src, ch);
-        run_actions(ch, actions, nactions);
-        *size = spz_table_to_file(c, ch.typed(), fractional_bits, out_fd, out_clamped);
-        *out_m = ch.n;
-    });
+    return spz_form(c, HostSrc{src}, actions, nactions, fractional_bits, out_fd, out_m, size, out_clamped, false);
 }
 
 int st_ply_spz_file(st_ctx *c, int32_t fd, const st_ply_header *h, int32_t element, const st_action *actions,
                     int32_t nactions, int32_t fractional_bits, int32_t out_fd, uint64_t *out_m, uint64_t *size,
                     uint64_t *out_clamped) {
-    return guard([&] {
-        ST_REQUIRE(c && h && fd >= 0 && out_m && size && (actions || nactions == 0), ST_ERR_ARG, "NULL argument");
-        ST_REQUIRE(fractional_bits >= 0 && fractional_bits <= 23, ST_ERR_ARG, "spz: fractional_bits must be 0..23");
-        sog_file_check(out_fd);
-        use_device(c);
-        Chain ch{c};
-        ply_chain(c, fd, h, element, ch);
-        run_actions(ch, actions, nactions);
-        *size = spz_table_to_file(c, ch.typed(), fractional_bits, out_fd, out_clamped);
-        *out_m = ch.n;
-    });
+    return spz_form(c, PlySrc{fd, h, element}, actions, nactions, fractional_bits, out_fd, out_m, size, out_clamped,
+                    false);
 }
 
 // the same three with the gzip member around the image, deflated on the device
 int st_dev_spz_gz_file(st_ctx *c, const st_ttable *t, int32_t fractional_bits, int32_t out_fd, uint64_t *size,
                        uint64_t *out_clamped) {
-    return guard([&] {
-        ST_REQUIRE(c && t && size, ST_ERR_ARG, "NULL argument");
-        ST_REQUIRE(fractional_bits >= 0 && fractional_bits <= 23, ST_ERR_ARG, "spz: fractional_bits must be 0..23");
-        check_src(t);
-        sog_file_check(out_fd);
-        use_device(c);
-        *size = spz_table_to_file(c, t, fractional_bits, out_fd, out_clamped, true);
-    });
+    uint64_t rows;
+    return spz_form(c, DevSrc{t}, nullptr, 0, fractional_bits, out_fd, &rows, size, out_clamped, true);
 }
 
 int st_spz_gz_file(st_ctx *c, const st_ttable *src, const st_action *actions, int32_t nactions,
                    int32_t fractional_bits, int32_t out_fd, uint64_t *out_m, uint64_t *size, uint64_t *out_clamped) {
-    return guard([&] {
-        ST_REQUIRE(c && src && out_m && size && (actions || nactions == 0), ST_ERR_ARG, "NULL argument");
-        ST_REQUIRE(fractional_bits >= 0 && fractional_bits <= 23, ST_ERR_ARG, "spz: fractional_bits must be 0..23");
-        check_src(src);
-        sog_file_check(out_fd);
-        use_device(c);
-        Chain ch{c};
-        upload_chain(c, src, ch);
-        run_actions(ch, actions, nactions);
-        *size = spz_table_to_file(c, ch.typed(), fractional_bits, out_fd, out_clamped, true);
-        *out_m = ch.n;
-    });
+    return spz_form(c, HostSrc{src}, actions, nactions, fractional_bits, out_fd, out_m, size, out_clamped, true);
 }
 
 int st_ply_spz_gz_file(st_ctx *c, int32_t fd, const st_ply_header *h, int32_t element, const st_action *actions,
                        int32_t nactions, int32_t fractional_bits, int32_t out_fd, uint64_t *out_m, uint64_t *size,
                        uint64_t *out_clamped) {
-    return guard([&] {
-        ST_REQUIRE(c && h && fd >= 0 && out_m && size && (actions || nactions == 0), ST_ERR_ARG, "NULL argument");
-        ST_REQUIRE(fractional_bits >= 0 && fractional_bits <= 23, ST_ERR_ARG, "spz: fractional_bits must be 0..23");
-        sog_file_check(out_fd);
-        use_device(c);
-        Chain ch{c};
-        ply_chain(c, fd, h, element, ch);
-        run_actions(ch, actions, nactions);
-        *size = spz_table_to_file(c, ch.typed(), fractional_bits, out_fd, out_clamped, true);
-        *out_m = ch.n;
-    });
-}
-
-// the parameter checks that need no table, before any work (the table's own follow in ksplat_params)
-static void ksplat_arg_check(int32_t mode, int32_t degree, float block_size) {
-    ST_REQUIRE(mode >= 0 && mode <= 2, ST_ERR_ARG, "ksplat: mode must be 0, 1 or 2");
-    ST_REQUIRE(degree >= -1 && degree <= 3, ST_ERR_ARG, "ksplat: degree must be -1..3");
-    ST_REQUIRE(block_size > 0.0f && block_size < __builtin_inff(), ST_ERR_ARG,
-               "ksplat: block_size must be finite and > 0 as a float32");
+    return spz_form(c, PlySrc{fd, h, element}, actions, nactions, fractional_bits, out_fd, out_m, size, out_clamped,
+                    true);
 }
 
 int st_dev_ksplat_file(st_ctx *c, const st_ttable *t, int32_t mode, int32_t degree, float block_size, float sh_min,
                        float sh_max, int32_t out_fd, uint64_t *size, uint64_t *out_clamped) {
-    return guard([&] {
-        ST_REQUIRE(c && t && size, ST_ERR_ARG, "NULL argument");
-        ksplat_arg_check(mode, degree, block_size);
-        check_src(t);
-        sog_file_check(out_fd);
-        use_device(c);
-        *size = ksplat_table_to_file(c, t, mode, degree, block_size, sh_min, sh_max, out_fd, out_clamped);
-    });
+    uint64_t rows;
+    return ksplat_form(c, DevSrc{t}, nullptr, 0, mode, degree, block_size, sh_min, sh_max, out_fd, &rows, size,
+                       out_clamped);
 }
 
 int st_ksplat_file(st_ctx *c, const st_ttable *src, const st_action *actions, int32_t nactions, int32_t mode,
                    int32_t degree, float block_size, float sh_min, float sh_max, int32_t out_fd, uint64_t *out_m,
                    uint64_t *size, uint64_t *out_clamped) {
-    return guard([&] {
-        ST_REQUIRE(c && src && out_m && size && (actions || nactions == 0), ST_ERR_ARG, "NULL argument");
-        ksplat_arg_check(mode, degree, block_size);
-        check_src(src);
-        sog_file_check(out_fd);
-        use_device(c);
-        Chain ch{c};
-        upload_chain(c, src, ch);
-        run_actions(ch, actions, nactions);
-        *size = ksplat_table_to_file(c, ch.typed(), mode, degree, block_size, sh_min, sh_max, out_fd, out_clamped);
-        *out_m = ch.n;
-    });
+    return ksplat_form(c, HostSrc{src}, actions, nactions, mode, degree, block_size, sh_min, sh_max, out_fd, out_m,
+                       size, out_clamped);
 }
 
 int st_ply_ksplat_file(st_ctx *c, int32_t fd, const st_ply_header *h, int32_t element, const st_action *actions,
                        int32_t nactions, int32_t mode, int32_t degree, float block_size, float sh_min, float sh_max,
                        int32_t out_fd, uint64_t *out_m, uint64_t *size, uint64_t *out_clamped) {
-    return guard([&] {
-        ST_REQUIRE(c && h && fd >= 0 && out_m && size && (actions || nactions == 0), ST_ERR_ARG, "NULL argument");
-        ksplat_arg_check(mode, degree, block_size);
-        sog_file_check(out_fd);
-        use_device(c);
-        Chain ch{c};
-        ply_chain(c, fd, h, element, ch);
-        run_actions(ch, actions, nactions);
-        *size = ksplat_table_to_file(c, ch.typed(), mode, degree, block_size, sh_min, sh_max, out_fd, out_clamped);
-        *out_m = ch.n;
-    });
+    return ksplat_form(c, PlySrc{fd, h, element}, actions, nactions, mode, degree, block_size, sh_min, sh_max, out_fd,
+                       out_m, size, out_clamped);
 }
 
 int st_ply_sog_bundle(st_ctx *c, int32_t fd, const st_ply_header *h, int32_t element, const st_action *actions,
                       int32_t nactions, int32_t iters, const double *draws, uint64_t ndraws, uint64_t *used,
                       uint16_t dos_time, uint16_t dos_date, uint8_t **out, uint64_t *out_size) {
     return guard([&] {
-        sog_chain(
-            c, [&](Chain &ch) {
-                ST_ARG(c && h && fd >= 0, "NULL argument");
-                ply_chain(c, fd, h, element, ch);
-            },
-            actions, nactions, iters, draws, ndraws, used, SogSink::buffer(out, out_size, dos_time, dos_date));
+        sog_chain(c, PlySrc{fd, h, element}, actions, nactions, iters, draws, ndraws, used,
+                  SogSink::buffer(out, out_size, dos_time, dos_date));
     });
 }
 
@@ -1216,7 +1130,7 @@ int st_sog_bundle_process(st_ctx *c, const st_ttable *src, const st_action *acti
                           const double *draws, uint64_t ndraws, uint64_t *used, uint16_t dos_time, uint16_t dos_date,
                           uint8_t **out, uint64_t *out_size) {
     return guard([&] {
-        sog_chain(c, host_loader(c, src), actions, nactions, iters, draws, ndraws, used,
+        sog_chain(c, HostSrc{src}, actions, nactions, iters, draws, ndraws, used,
                   SogSink::buffer(out, out_size, dos_time, dos_date));
     });
 }
@@ -1225,7 +1139,7 @@ int st_sog_process(st_ctx *c, const st_ttable *src, const st_action *actions, in
                    const double *draws, uint64_t ndraws, uint64_t *used, st_sog_meta *meta,
                    const st_sog_textures *out) {
     return guard([&] {
-        sog_chain(c, host_loader(c, src), actions, nactions, iters, draws, ndraws, used, SogSink::textures(meta, out));
+        sog_chain(c, HostSrc{src}, actions, nactions, iters, draws, ndraws, used, SogSink::textures(meta, out));
     });
 }
 

@@ -5,6 +5,7 @@ numpy arrays; ``dev_*`` entry points take torch CUDA (HIP) tensors and pass
 their device pointers, running on torch's current stream.  There is no CPU
 fallback: constructing a Context without a gfx950 device raises.
 """
+import contextlib
 import ctypes
 import weakref
 import os
@@ -638,6 +639,24 @@ class _OutFd:
             os.close(self.fd)
 
 
+@contextlib.contextmanager
+def _ply_in(path):
+    """a .ply file opened read-only, its header read: (descriptor, PlyHeader) while the block runs"""
+    fd = os.open(path, os.O_RDONLY)
+    try:
+        h = PlyHeader()
+        check(lib().st_ply_read_header(ctypes.c_int32(fd), ctypes.byref(h)))
+        yield fd, h
+    finally:
+        os.close(fd)
+
+
+def _host_table(cols):
+    """host columns (a dict or a list of (name, numpy array)) -> (the list, its st_ttable)"""
+    items = list(cols.items()) if isinstance(cols, dict) else list(cols)
+    return items, make_ttable(items, len(items[0][1]) if items else 0)
+
+
 READER_COLS = ['x', 'y', 'z', 'scale_0', 'scale_1', 'scale_2', 'f_dc_0', 'f_dc_1', 'f_dc_2', 'opacity',
                'rot_0', 'rot_1', 'rot_2', 'rot_3']
 
@@ -1095,11 +1114,10 @@ class Context:
     def sog_process(self, cols, actions, iters, draws):
         """processDataTable then writeSog's textures + meta on a host table of any column types
         (list of (name, array) or dict): (textures, meta, draws used) as sog()"""
-        items = list(cols.items()) if isinstance(cols, dict) else list(cols)
+        items, t = _host_table(cols)
         names = [k for k, _ in items]
         first_missing = next((i for i in range(45) if f'f_rest_{i}' not in names), -1)
         C = {9: 3, 24: 8, -1: 15}.get(first_missing, 0)
-        t = make_ttable(items)
         tex, out, _ = _sog_out(t.n, C)
         meta = SogMeta()
         used = ctypes.c_uint64(0)
@@ -1117,8 +1135,7 @@ class Context:
 
     def sog_bundle_process(self, cols, actions, iters, draws, dos_time, dos_date):
         """processDataTable then writeSog to a .sog bundle, any column types: (archive, draws used)"""
-        items = list(cols.items()) if isinstance(cols, dict) else list(cols)
-        t = make_ttable(items)
+        _, t = _host_table(cols)
         acts = make_actions(actions)
         used = ctypes.c_uint64(0)
         out, size = ctypes.c_void_p(), ctypes.c_uint64(0)
@@ -1142,10 +1159,7 @@ class Context:
         resident: st_ply_read_resident -- the numpy columns stay unfilled (the values live in HBM) until
         materialize(column) or a host form other than writeSog's reads them; keep them alive until then,
         or forget() them"""
-        fd = os.open(path, os.O_RDONLY)
-        try:
-            h = PlyHeader()
-            check(lib().st_ply_read_header(ctypes.c_int32(fd), ctypes.byref(h)))
+        with _ply_in(path) as (fd, h):
             out = []
             read = lib().st_ply_read_resident if resident else lib().st_ply_read
             for ei, (name, count, props) in enumerate(h.layout()):
@@ -1157,8 +1171,6 @@ class Context:
                         weakref.finalize(a, _forget_column, weakref.ref(self), a.ctypes.data)
                 out.append((name, cols))
             return h.comment_list(), out
-        finally:
-            os.close(fd)
 
     def materialize(self, col):
         """a resident read's column filled from HBM (st_ply_materialize); no-op for any other array"""
@@ -1253,10 +1265,7 @@ class Context:
         import torch
         tmap = {np.int8: torch.int8, np.uint8: torch.uint8, np.int16: torch.int16, np.uint16: torch.uint16,
                 np.int32: torch.int32, np.uint32: torch.uint32, np.float32: torch.float32, np.float64: torch.float64}
-        fd = os.open(path, os.O_RDONLY)
-        try:
-            h = PlyHeader()
-            check(lib().st_ply_read_header(ctypes.c_int32(fd), ctypes.byref(h)))
+        with _ply_in(path) as (fd, h):
             out = []
             for ei, (name, count, props) in enumerate(h.layout()):
                 cols = {pn: torch.empty(count, dtype=tmap[dt], device=device) for pn, dt in props}
@@ -1264,8 +1273,6 @@ class Context:
                 check(lib().st_dev_ply_read(self.h, ctypes.c_int32(fd), ctypes.byref(h), ctypes.c_int32(ei), ptrs))
                 out.append((name, cols))
             return h.comment_list(), out
-        finally:
-            os.close(fd)
 
     # ---- the other input formats (index.ts:52-76) ---------------------------------------
     def _reader_out(self, n, nsh, device):
@@ -1494,9 +1501,9 @@ class Context:
 
     def filter_nan(self, cols):
         """filterNaN on host columns (list of (name, numpy array), any type) -> the surviving rows"""
-        items = list(cols.items()) if isinstance(cols, dict) else list(cols)
+        items, ts = _host_table(cols)
         out = [(k, np.empty_like(a)) for k, a in items]
-        ts, td = make_ttable(items), make_ttable(out)
+        td = make_ttable(out)
         m = ctypes.c_uint64()
         check(lib().st_filter_nan(self.h, ctypes.byref(ts), ctypes.byref(td), ctypes.byref(m)))
         return [(k, a[:m.value].copy()) for k, a in out]
@@ -1532,12 +1539,11 @@ class Context:
 
     def compressed_ply(self, cols, actions):
         """processDataTable then writeCompressedPly's device part, one upload: (m, chunk, vertex, sh)"""
-        items = list(cols.items()) if isinstance(cols, dict) else list(cols)
-        n = len(items[0][1]) if items else 0
+        _, ts = _host_table(cols)
+        n = ts.n
         chunk = np.zeros(max(1, (n + 255) // 256 * 18), np.float32)
         vertex = np.zeros(max(1, n * 4), np.uint32)
         sh = np.zeros(max(1, n * 45), np.uint8)
-        ts = make_ttable(items, n)
         acts = make_actions(actions)
         m, C = ctypes.c_uint64(), ctypes.c_int32()
         check(lib().st_compressed_ply(self.h, ctypes.byref(ts), acts, ctypes.c_int32(len(actions)), _vp(chunk),
@@ -1557,10 +1563,7 @@ class Context:
     def ply_compressed_ply(self, path, actions, element=-1):
         """readPly + processDataTable + writeCompressedPly's arrays from the file, resident in HBM
         (st_ply_compressed_ply): (m, chunk, vertex, sh)"""
-        fd = os.open(path, os.O_RDONLY)
-        try:
-            h = PlyHeader()
-            check(lib().st_ply_read_header(ctypes.c_int32(fd), ctypes.byref(h)))
+        with _ply_in(path) as (fd, h):
             ei = element if element >= 0 else [e[0] for e in h.layout()].index('vertex')
             n = h.layout()[ei][1]
             chunk = np.zeros(max(1, (n + 255) // 256 * 18), np.float32)
@@ -1571,8 +1574,6 @@ class Context:
             check(lib().st_ply_compressed_ply(self.h, ctypes.c_int32(fd), ctypes.byref(h), ctypes.c_int32(element),
                                               acts, ctypes.c_int32(len(actions)), _vp(chunk), _vp(vertex), _vp(sh),
                                               ctypes.byref(m), ctypes.byref(C)))
-        finally:
-            os.close(fd)
         m, C = m.value, C.value
         return m, chunk[:(m + 255) // 256 * 18], vertex[:m * 4], sh[:m * 3 * C]
 
@@ -1580,10 +1581,7 @@ class Context:
         """readPly + processDataTable + writeCompressedPly into out_path (st_ply_compressed_ply_file:
         the arrays written at offsets as they leave HBM; the file opened without O_TRUNC, cut to
         length by the library): (m, sh_coeffs, file bytes)"""
-        fd = os.open(path, os.O_RDONLY)
-        try:
-            h = PlyHeader()
-            check(lib().st_ply_read_header(ctypes.c_int32(fd), ctypes.byref(h)))
+        with _ply_in(path) as (fd, h):
             acts = make_actions(actions)
             m, C, size = ctypes.c_uint64(), ctypes.c_int32(), ctypes.c_uint64()
             ofd = os.open(out_path, os.O_WRONLY | os.O_CREAT, 0o644)
@@ -1594,16 +1592,12 @@ class Context:
                                                        ctypes.byref(m), ctypes.byref(C), ctypes.byref(size)))
             finally:
                 os.close(ofd)
-        finally:
-            os.close(fd)
         return m.value, C.value, size.value
 
     def compressed_ply_file(self, cols, actions, out_path, version=None):
         """processDataTable + writeCompressedPly of a host table into out_path (st_compressed_ply_file):
         (m, sh_coeffs, file bytes)"""
-        items = list(cols.items()) if isinstance(cols, dict) else list(cols)
-        n = len(items[0][1]) if items else 0
-        ts = make_ttable(items, n)
+        _, ts = _host_table(cols)
         acts = make_actions(actions)
         m, C, size = ctypes.c_uint64(), ctypes.c_int32(), ctypes.c_uint64()
         ofd = os.open(out_path, os.O_WRONLY | os.O_CREAT, 0o644)
@@ -1665,8 +1659,7 @@ class Context:
         """processDataTable + writePly of a host table (list of (name, numpy array) or a dict) into
         `out`, a path or a descriptor (st_ply_file): (rows written, file bytes).  The input arrays are
         not changed"""
-        items = list(cols.items()) if isinstance(cols, dict) else list(cols)
-        ts = make_ttable(items, len(items[0][1]) if items else 0)
+        _, ts = _host_table(cols)
         acts = make_actions(actions)
         cs, nc = _comments_arg(comments)
         m, size = ctypes.c_uint64(), ctypes.c_uint64()
@@ -1678,10 +1671,7 @@ class Context:
     def ply_ply_file(self, path, actions, out, comments=(), element=-1):
         """the CLI's `in.ply [actions] out.ply` (st_ply_ply_file): the element's rows stay in HBM from
         ingest to output: (rows written, file bytes)"""
-        fd = os.open(path, os.O_RDONLY)
-        try:
-            h = PlyHeader()
-            check(lib().st_ply_read_header(ctypes.c_int32(fd), ctypes.byref(h)))
+        with _ply_in(path) as (fd, h):
             acts = make_actions(actions)
             cs, nc = _comments_arg(comments)
             m, size = ctypes.c_uint64(), ctypes.c_uint64()
@@ -1689,8 +1679,6 @@ class Context:
                 check(lib().st_ply_ply_file(self.h, ctypes.c_int32(fd), ctypes.byref(h), ctypes.c_int32(element), acts,
                                             ctypes.c_int32(len(actions)), cs, nc, ofd, ctypes.byref(m),
                                             ctypes.byref(size)))
-        finally:
-            os.close(fd)
         return m.value, size.value
 
     # ---- writeCsv (write-csv.ts) ---------------------------------------------------------
@@ -1719,8 +1707,7 @@ class Context:
         """processDataTable + writeCsv of a host table (list of (name, numpy array) or a dict) into
         `out`, a path or a descriptor (st_csv_file): (rows written, file bytes).  The input arrays are
         not changed"""
-        items = list(cols.items()) if isinstance(cols, dict) else list(cols)
-        ts = make_ttable(items, len(items[0][1]) if items else 0)
+        _, ts = _host_table(cols)
         acts = make_actions(actions)
         m, size = ctypes.c_uint64(), ctypes.c_uint64()
         with _OutFd(out) as fd:
@@ -1731,17 +1718,12 @@ class Context:
     def ply_csv_file(self, path, actions, out, element=-1):
         """the CLI's `in.ply [actions] out.csv` (st_ply_csv_file): the element's rows stay in HBM from
         ingest to output: (rows written, file bytes)"""
-        fd = os.open(path, os.O_RDONLY)
-        try:
-            h = PlyHeader()
-            check(lib().st_ply_read_header(ctypes.c_int32(fd), ctypes.byref(h)))
+        with _ply_in(path) as (fd, h):
             acts = make_actions(actions)
             m, size = ctypes.c_uint64(), ctypes.c_uint64()
             with _OutFd(out) as ofd:
                 check(lib().st_ply_csv_file(self.h, ctypes.c_int32(fd), ctypes.byref(h), ctypes.c_int32(element), acts,
                                             ctypes.c_int32(len(actions)), ofd, ctypes.byref(m), ctypes.byref(size)))
-        finally:
-            os.close(fd)
         return m.value, size.value
 
     # ---- the .splat and .spz writers (st_abi.h, "the .splat and .spz writers") ------------------
@@ -1792,8 +1774,7 @@ class Context:
     def splat_file(self, cols, actions, out):
         """processDataTable + the .splat writer on a host table (list of (name, numpy array) or a
         dict) into `out`, a path or a descriptor (st_splat_file): (rows written, file bytes)"""
-        items = list(cols.items()) if isinstance(cols, dict) else list(cols)
-        ts = make_ttable(items, len(items[0][1]) if items else 0)
+        _, ts = _host_table(cols)
         acts = make_actions(actions)
         m, size = ctypes.c_uint64(), ctypes.c_uint64()
         with _OutFd(out) as fd:
@@ -1804,17 +1785,12 @@ class Context:
     def ply_splat_file(self, path, actions, out, element=-1):
         """`in.ply [actions] out.splat` (st_ply_splat_file): the element's rows stay in HBM from
         ingest to output: (rows written, file bytes)"""
-        fd = os.open(path, os.O_RDONLY)
-        try:
-            h = PlyHeader()
-            check(lib().st_ply_read_header(ctypes.c_int32(fd), ctypes.byref(h)))
+        with _ply_in(path) as (fd, h):
             acts = make_actions(actions)
             m, size = ctypes.c_uint64(), ctypes.c_uint64()
             with _OutFd(out) as ofd:
                 check(lib().st_ply_splat_file(self.h, ctypes.c_int32(fd), ctypes.byref(h), ctypes.c_int32(element), acts,
                                               ctypes.c_int32(len(actions)), ofd, ctypes.byref(m), ctypes.byref(size)))
-        finally:
-            os.close(fd)
         return m.value, size.value
 
     @staticmethod
@@ -1876,8 +1852,7 @@ class Context:
         """processDataTable + the .spz writer on a host table (list of (name, numpy array) or a dict)
         into `out` (st_spz_file; deflate='device': st_spz_gz_file): (rows written, file bytes, position
         values clamped)"""
-        items = list(cols.items()) if isinstance(cols, dict) else list(cols)
-        ts = make_ttable(items, len(items[0][1]) if items else 0)
+        _, ts = _host_table(cols)
         acts = make_actions(actions)
 
         def call(fd, gz):
@@ -1895,17 +1870,12 @@ class Context:
         acts = make_actions(actions)
 
         def call(ofd, gz):
-            fd = os.open(path, os.O_RDONLY)
-            try:
-                h = PlyHeader()
-                check(lib().st_ply_read_header(ctypes.c_int32(fd), ctypes.byref(h)))
+            with _ply_in(path) as (fd, h):
                 m, size, clamped = ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_uint64()
                 form = lib().st_ply_spz_gz_file if gz else lib().st_ply_spz_file
                 check(form(self.h, ctypes.c_int32(fd), ctypes.byref(h), ctypes.c_int32(element), acts,
                            ctypes.c_int32(len(actions)), ctypes.c_int32(fractional_bits), ofd, ctypes.byref(m),
                            ctypes.byref(size), ctypes.byref(clamped)))
-            finally:
-                os.close(fd)
             return m.value, size.value, clamped.value
         return self._spz_out(call, out, gzip_level, deflate)
 
@@ -1971,8 +1941,7 @@ class Context:
     def ksplat_file(self, cols, actions, out, mode=1, degree=-1, block_size=5.0, sh_min=-1.5, sh_max=1.5):
         """processDataTable + the .ksplat writer on a host table (list of (name, numpy array) or a dict)
         into `out` (st_ksplat_file): (rows written, file bytes, position values clamped)"""
-        items = list(cols.items()) if isinstance(cols, dict) else list(cols)
-        ts = make_ttable(items, len(items[0][1]) if items else 0)
+        _, ts = _host_table(cols)
         acts = make_actions(actions)
         m, size, clamped = ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_uint64()
         with _OutFd(out) as fd:
@@ -1985,18 +1954,13 @@ class Context:
         """`in.ply [actions] out.ksplat` (st_ply_ksplat_file): the element's rows stay in HBM from ingest
         to the image: (rows written, file bytes, position values clamped)"""
         acts = make_actions(actions)
-        fd = os.open(path, os.O_RDONLY)
-        try:
-            h = PlyHeader()
-            check(lib().st_ply_read_header(ctypes.c_int32(fd), ctypes.byref(h)))
+        with _ply_in(path) as (fd, h):
             m, size, clamped = ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_uint64()
             with _OutFd(out) as ofd:
                 check(lib().st_ply_ksplat_file(self.h, ctypes.c_int32(fd), ctypes.byref(h), ctypes.c_int32(element), acts,
                                                ctypes.c_int32(len(actions)), ctypes.c_int32(mode), ctypes.c_int32(degree),
                                                ctypes.c_float(block_size), ctypes.c_float(sh_min), ctypes.c_float(sh_max), ofd,
                                                ctypes.byref(m), ctypes.byref(size), ctypes.byref(clamped)))
-        finally:
-            os.close(fd)
         return m.value, size.value, clamped.value
 
     # ---- writeHtml (write-html.ts) -------------------------------------------------------
@@ -2018,8 +1982,7 @@ class Context:
         """processDataTable + writeHtml of a host table (list of (name, numpy array) or a dict) into
         `out`, a path or a descriptor (st_html_file).  template: the viewer's (html, css, js), str or
         UTF-8 bytes -> (rows embedded, sh_coeffs, file bytes).  The input arrays are not changed"""
-        items = list(cols.items()) if isinstance(cols, dict) else list(cols)
-        ts = make_ttable(items, len(items[0][1]) if items else 0)
+        _, ts = _host_table(cols)
         acts = make_actions(actions)
         enc = [t.encode('utf-8') if isinstance(t, str) else bytes(t) for t in template]
         m, C, size = ctypes.c_uint64(), ctypes.c_int32(), ctypes.c_uint64()
@@ -2033,10 +1996,7 @@ class Context:
                       element=-1):
         """the CLI's `in.ply [actions] out.html` (st_ply_html_file): the element's rows stay in HBM from
         ingest to the text: (rows embedded, sh_coeffs, file bytes)"""
-        fd = os.open(path, os.O_RDONLY)
-        try:
-            h = PlyHeader()
-            check(lib().st_ply_read_header(ctypes.c_int32(fd), ctypes.byref(h)))
+        with _ply_in(path) as (fd, h):
             acts = make_actions(actions)
             enc = [t.encode('utf-8') if isinstance(t, str) else bytes(t) for t in template]
             m, C, size = ctypes.c_uint64(), ctypes.c_int32(), ctypes.c_uint64()
@@ -2045,17 +2005,12 @@ class Context:
                                              ctypes.c_int32(len(actions)), enc[0], enc[1], enc[2], _vec3(camera),
                                              _vec3(target), ofd, version.encode() if version else None,
                                              ctypes.byref(m), ctypes.byref(C), ctypes.byref(size)))
-        finally:
-            os.close(fd)
         return m.value, C.value, size.value
 
     def ply_sog_bundle(self, path, actions, iters, draws, dos_time, dos_date, element=-1):
         """readPly + processDataTable + writeSog to .sog bytes from the file (st_ply_sog_bundle):
         (archive bytes, draws used)"""
-        fd = os.open(path, os.O_RDONLY)
-        try:
-            h = PlyHeader()
-            check(lib().st_ply_read_header(ctypes.c_int32(fd), ctypes.byref(h)))
+        with _ply_in(path) as (fd, h):
             acts = make_actions(actions)
             draws = np.ascontiguousarray(draws, np.float64)
             used, size = ctypes.c_uint64(), ctypes.c_uint64()
@@ -2064,8 +2019,6 @@ class Context:
                                           ctypes.c_int32(len(actions)), ctypes.c_int32(iters), _vp(draws),
                                           ctypes.c_uint64(len(draws)), ctypes.byref(used), ctypes.c_uint16(dos_time),
                                           ctypes.c_uint16(dos_date), ctypes.byref(out), ctypes.byref(size)))
-        finally:
-            os.close(fd)
         return _take(out, size), used.value
 
     def dev_filter_finite_t(self, cols, out_idx):

@@ -223,6 +223,48 @@ def test_spz_file_raw_and_gzipped(ctx, tmp_path, monkeypatch, stream_case):
     assert first_difference(h.read_bytes(), want) is None
 
 
+@pytest.fixture(scope='module')
+def ring_case():
+    """220,753 rows of degree 0 and their .splat rows, made once: every case below is a prefix of them"""
+    cols = ordinary(np.random.default_rng(220_753), 220_753, 0)
+    return cols, ref.splat_rows([(k, a[:163_841]) for k, a in cols]).tobytes()
+
+
+@pytest.mark.parametrize('form, n', [('splat', 32_768),    # one slot exactly: a full last piece, none after it
+                                     ('splat', 32_769),    # a second piece of 32 bytes
+                                     ('splat', 163_841),   # six pieces: slots 0 and 1 are taken a second time
+                                     ('spz', 220_752),     # 16 + 19 n = 4 slots exactly, copied down as they are
+                                     ('spz', 220_753)])    # the fifth piece takes slot 0 again
+def test_file_forms_at_the_ring_slot_boundaries(ctx, tmp_path, monkeypatch, ring_case, form, n):
+    """outputs that end on a 1 MiB slot boundary, one byte run past it, and more pieces than the ring
+    has slots (4), into a longer file at a non-zero position"""
+    monkeypatch.setenv('ST_CPF_SLOT_MB', '1')
+    table, rows = ring_case
+    cols = [(k, a[:n]) for k, a in table]
+    if form == 'splat':
+        want, result = rows[:32 * n], 32 * n
+    else:
+        want, want_clamped = ref.spz_image(cols, 12)
+        assert len(want) == 16 + 19 * n
+        result = (n, len(want), want_clamped)
+    assert (len(want) % (1 << 20) == 0) == (n in (32_768, 220_752))
+    p = tmp_path / f'at.{form}'
+    p.write_bytes(b'\xee' * (len(want) + 4097))
+    fd = os.open(str(p), os.O_RDWR)
+    try:
+        os.lseek(fd, 37, os.SEEK_SET)
+        if form == 'splat':
+            assert ctx.dev_splat_file(to_dev(cols), fd) == result
+        else:
+            assert ctx.dev_spz_file(to_dev(cols), fd, gzip_level=0) == result
+        assert os.lseek(fd, 0, os.SEEK_CUR) == 37 + len(want) == os.fstat(fd).st_size
+    finally:
+        os.close(fd)
+    got = p.read_bytes()
+    assert got[:37] == b'\xee' * 37 and len(got) == 37 + len(want)
+    assert first_difference(got[37:], want) is None
+
+
 @pytest.mark.parametrize('flags', [os.O_RDONLY, os.O_WRONLY | os.O_APPEND])
 def test_file_forms_refuse_descriptor(ctx, tmp_path, flags):
     cols = ordinary(np.random.default_rng(3), 100, 3)
