@@ -1086,6 +1086,79 @@ int st_ply_ksplat_file(st_ctx *ctx, int32_t fd, const st_ply_header *h, int32_t 
                        int32_t nactions, int32_t mode, int32_t degree, float block_size, float sh_min, float sh_max,
                        int32_t out_fd, uint64_t *out_m, uint64_t *size, uint64_t *out_clamped);
 
+/* ---- inflating a gzip member on the device: INFLATE (RFC 1951) for the .spz reader --------------
+ * readSpz gunzips its file first (read-spz.ts:50-75).  These calls do that on the device for ANY
+ * deflate stream -- one zlib stream of many dynamic-code blocks with back-references through the
+ * 32 KiB window, not only the segments st_dev_gzip writes -- by a method whose result never rests
+ * on a guess (csrc/st_inflate.h holds every rule as a host/device function, and a serial host form
+ * of the same steps):
+ *   find     the compressed bytes are cut into chunks of chunk_bytes.  For every chunk but the
+ *            first: the first bit position in the chunk at which a NON-FINAL dynamic-code block
+ *            header parses completely (BTYPE 2, HLIT and HDIST at most 29, a complete code-length
+ *            code, a valid length sequence, a length for symbol 256, both codes complete or zlib's
+ *            one-code case).  A chunk may have none.  Stored and fixed blocks are not looked for.
+ *   size     one decoder per candidate, and one at bit 0, decodes block after block and counts
+ *            bytes.  After a block that ends at bit p it stops if the block was final (FINAL) or
+ *            if p is the candidate of a later chunk (JOINED); candidates below p are passed.
+ *   chain    from chunk 0 along the JOINED links to FINAL.  Only these decoders are kept: each
+ *            started where the true decode has a block boundary, so the result is the sequential
+ *            inflate whatever the finder returned.  A running sum gives each its output offset.
+ *   write    the kept decoders decode again into 16-bit symbols: a byte, or 256 + i for a
+ *            reference to byte i of the 32 KiB before the decoder's first byte (copies carry such
+ *            markers along).
+ *   windows  kept chunk after kept chunk, the last 32 KiB of each become bytes; then every other
+ *            symbol does, all at once.
+ * A decoder gives up after ST_INFLATE_BUDGET * chunk_bytes coded symbols (stored blocks cost none).
+ *
+ * DECLINED.  These calls return ST_OK, a negative st_status (a bad argument, a HIP error), or
+ * ST_DECLINED (1, no message): the device path does not take this input, and the caller inflates it
+ * some other way.  Declined: any parse error zlib would report, a decoder over its budget, a chain
+ * that breaks, bytes after the final block, an output that is not `expect` bytes, a CRC-32 or ISIZE
+ * that does not match, a second member, reserved FLG bits, a method other than 8, a header longer
+ * than 4,096 bytes (st_dev_gunzip).  After ST_DECLINED nothing is promised about the output bytes.
+ *
+ * st_gzip_member_layout (host only): RFC 1952's header with FEXTRA, FNAME, FCOMMENT and FHCRC
+ * stepped over -> where the deflate stream lies in the member and the trailer's CRC-32 and ISIZE.
+ * st_inflate_head (host only): the first `want` bytes of a raw deflate stream, serially; *got = how
+ * many there are.  The .spz reader takes the image's 16-byte header this way, so the rows and the
+ * image size are known before anything is allocated.
+ * st_dev_inflate: the raw deflate stream dev_in[0..n) into dev_out[0..expect).  st_dev_gunzip: the
+ * same for one gzip member, with the trailer checked.  chunk_bytes: 0 = ST_INFLATE_CHUNK; any value
+ * from 256 up is taken (below: ST_ERR_ARG).  Device pointers of ANY alignment; no byte outside
+ * [dev_out, dev_out + expect) is written.  stats (nullable) is filled as far as the call got.
+ * Both wait for the kernels.
+ * st_spz_gz_layout (host only): row count and f_rest count of a gzipped .spz FILE from its member
+ * layout and its first 16 inflated bytes (st_spz_layout's checks on them, the image size being the
+ * trailer's ISIZE); *image_bytes = that size.  Whatever st_spz_layout would refuse is ST_DECLINED
+ * here: the caller's host path then reports it in its own words.
+ * st_spz_gz_read / st_dev_spz_gz_read: st_spz_read / st_dev_spz_read from the FILE's bytes (host):
+ * layout, head, upload, st_dev_gunzip's steps into HBM, then the same decode kernel. */
+#define ST_DECLINED 1
+#define ST_INFLATE_CHUNK 65536
+#define ST_INFLATE_BUDGET 512
+typedef struct st_inflate_stats {
+    uint64_t chunks;         /* chunks of compressed bytes */
+    uint64_t candidates;     /* chunks (after the first) in which the finder found a start */
+    uint64_t kept;           /* decoders on the chain */
+    uint64_t discarded;      /* decoders run and not kept: 1 + candidates - kept */
+    uint64_t markers;        /* symbols of the write pass that refer to the previous window */
+    uint64_t stored_blocks;  /* blocks the kept decoders read, by BTYPE */
+    uint64_t fixed_blocks;
+    uint64_t dynamic_blocks;
+} st_inflate_stats;
+int st_gzip_member_layout(const uint8_t *host, uint64_t n, uint64_t *stream_off, uint64_t *stream_len, uint32_t *crc,
+                          uint32_t *isize);
+int st_inflate_head(const uint8_t *host_stream, uint64_t n, uint8_t *out, uint64_t want, uint64_t *got);
+int st_dev_inflate(st_ctx *ctx, const uint8_t *dev_in, uint64_t n, uint8_t *dev_out, uint64_t expect,
+                   uint64_t chunk_bytes, st_inflate_stats *stats);
+int st_dev_gunzip(st_ctx *ctx, const uint8_t *dev_in, uint64_t n, uint8_t *dev_out, uint64_t expect,
+                  uint64_t chunk_bytes, st_inflate_stats *stats);
+int st_spz_gz_layout(const uint8_t *file, uint64_t len, uint64_t *n, int32_t *nsh, uint64_t *image_bytes);
+int st_spz_gz_read(st_ctx *ctx, const uint8_t *file, uint64_t len, float *const *host_cols, uint64_t chunk_bytes,
+                   st_inflate_stats *stats);
+int st_dev_spz_gz_read(st_ctx *ctx, const uint8_t *file, uint64_t len, float *const *cols, uint64_t chunk_bytes,
+                       st_inflate_stats *stats);
+
 #ifdef __cplusplus
 }
 #endif

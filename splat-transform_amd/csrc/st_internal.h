@@ -479,6 +479,12 @@ uint64_t spz_image_dev(st_ctx *c, const WrTable &W, int fractional_bits, uint8_t
 // returns its size; above cap: ST_ERR_ARG and nothing is written.  Both wait for their kernels.
 uint64_t deflate_dev(st_ctx *c, const uint8_t *dev_in, uint64_t n, uint8_t *dev_out, uint64_t cap);
 uint64_t gzip_dev(st_ctx *c, const uint8_t *dev_in, uint64_t n, uint8_t *dev_out, uint64_t cap);
+// st_inflate.hip: the raw deflate stream / gzip member dev_in[0..n) into dev_out[0..expect); false =
+// declined (st_abi.h, "inflating a gzip member on the device").  Both wait for the kernels.
+bool inflate_dev(st_ctx *c, const uint8_t *dev_in, uint64_t n, uint8_t *dev_out, uint64_t expect, uint64_t chunk_bytes,
+                 st_inflate_stats *stats);
+bool gunzip_dev(st_ctx *c, const uint8_t *dev_in, uint64_t n, uint8_t *dev_out, uint64_t expect, uint64_t chunk_bytes,
+                st_inflate_stats *stats);
 
 // the .ksplat writer (st_ksplat_write.hip; the rules: st_abi.h, "the .ksplat writer").  ksplat_params
 // checks mode, degree (-1: the table's own), block size and harmonics range against a table picked

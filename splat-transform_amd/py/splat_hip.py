@@ -138,6 +138,8 @@ EXPORTS = [
     'st_ksplat_file', 'st_ply_ksplat_file',
     'st_deflate_bound', 'st_gzip_bound', 'st_dev_deflate', 'st_dev_gzip', 'st_dev_spz_gz_file', 'st_spz_gz_file',
     'st_ply_spz_gz_file',
+    'st_gzip_member_layout', 'st_inflate_head', 'st_dev_inflate', 'st_dev_gunzip', 'st_spz_gz_layout', 'st_spz_gz_read',
+    'st_dev_spz_gz_read',
 ]
 
 
@@ -732,6 +734,59 @@ def spz_inflate(data):
     return gzip.decompress(data)
 
 
+ST_DECLINED = 1
+INFLATE_CHUNK = 65536
+INFLATE_BUDGET = 512
+
+
+class InflateStats(ctypes.Structure):
+    """st_inflate_stats"""
+    _fields_ = [(k, ctypes.c_uint64) for k in ('chunks', 'candidates', 'kept', 'discarded', 'markers', 'stored_blocks',
+                                               'fixed_blocks', 'dynamic_blocks')]
+
+    def dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+def _declined(rc):
+    """True for ST_DECLINED, False for ST_OK; an error raises"""
+    if rc == ST_DECLINED:
+        return True
+    check(rc)
+    return False
+
+
+def gzip_member_layout(data):
+    """st_gzip_member_layout: (stream offset, stream bytes, CRC-32, ISIZE) of one gzip member, or None
+    when the device path does not take its header (host only)"""
+    data = bytes(data)
+    off, length, crc, isize = ctypes.c_uint64(0), ctypes.c_uint64(0), ctypes.c_uint32(0), ctypes.c_uint32(0)
+    if _declined(lib().st_gzip_member_layout(data, ctypes.c_uint64(len(data)), ctypes.byref(off), ctypes.byref(length),
+                                             ctypes.byref(crc), ctypes.byref(isize))):
+        return None
+    return off.value, length.value, crc.value, isize.value
+
+
+def inflate_head(stream, want):
+    """st_inflate_head: the first `want` bytes of a raw deflate stream (fewer when it ends first), or
+    None when the stream is broken before them (host only, serial)"""
+    stream = bytes(stream)
+    out, got = ctypes.create_string_buffer(max(want, 1)), ctypes.c_uint64(0)
+    if _declined(lib().st_inflate_head(stream, ctypes.c_uint64(len(stream)), out, ctypes.c_uint64(want), ctypes.byref(got))):
+        return None
+    return out.raw[:got.value]
+
+
+def spz_gz_layout(data):
+    """st_spz_gz_layout: (rows, f_rest columns, image bytes) of a gzipped .spz file's bytes, or None
+    when the device path declines it (host only)"""
+    n, nsh, size = ctypes.c_uint64(0), ctypes.c_int32(0), ctypes.c_uint64(0)
+    if _declined(lib().st_spz_gz_layout(data, ctypes.c_uint64(len(data)), ctypes.byref(n), ctypes.byref(nsh),
+                                        ctypes.byref(size))):
+        return None
+    return n.value, nsh.value, size.value
+
+
 def spz_image_size(n, sh_coeffs):
     """the bytes of a raw .spz image of n splats with sh_coeffs (0, 3, 8 or 15) coefficients per
     channel: 16 + n * (19 + 3 * sh_coeffs); 0 for a bad argument (st_spz_image_size; host only)"""
@@ -924,6 +979,8 @@ class Context:
             except RuntimeError:
                 pass  # no device: st_ctx_create reports it
         self.h = ctypes.c_void_p()
+        self.last_inflate = None        # 'host' or 'device': the way the last read_spz / read_spz_dev went
+        self.last_inflate_stats = None  # st_inflate_stats of the last device inflate, as far as it got
         check(lib().st_ctx_create(ctypes.c_int32(device), ctypes.byref(self.h)))
 
     def close(self):
@@ -1240,6 +1297,28 @@ class Context:
         """st_dev_gzip: one gzip member around that stream (spz_deflate's header, CRC-32, size)"""
         return self._dev_deflate(lib().st_dev_gzip, data, out, n)
 
+    def _dev_inflate(self, fn, data, out, n, expect, chunk_bytes):
+        n = data.numel() if n is None else n
+        expect = out.numel() if expect is None else expect
+        if expect > out.numel() or n > data.numel():
+            raise ValueError('more bytes than the tensor holds')
+        st = InflateStats()
+        declined = _declined(fn(self.h, _ptr(data), ctypes.c_uint64(n), _ptr(out), ctypes.c_uint64(expect),
+                                ctypes.c_uint64(chunk_bytes), ctypes.byref(st)))
+        self.last_inflate_stats = st.dict()
+        return None if declined else st.dict()
+
+    def dev_inflate(self, data, out, n=None, expect=None, chunk_bytes=0):
+        """st_dev_inflate: the raw deflate stream in the first n bytes of the device uint8 tensor `data`
+        into the first `expect` bytes of the device uint8 tensor `out` (defaults: all of both), both of
+        any alignment -> the statistics as a dict, or None when the device path DECLINES the stream
+        (nothing is then promised about `out`; last_inflate_stats holds what was counted)"""
+        return self._dev_inflate(lib().st_dev_inflate, data, out, n, expect, chunk_bytes)
+
+    def dev_gunzip(self, data, out, n=None, expect=None, chunk_bytes=0):
+        """st_dev_gunzip: the same for one gzip member; its CRC-32 and ISIZE are checked"""
+        return self._dev_inflate(lib().st_dev_gunzip, data, out, n, expect, chunk_bytes)
+
     def dev_sog_bundle_view(self, meta, count, tex, dos_time, dos_date):
         """as dev_sog_bundle without the copy: (address, size) of the context's pinned archive"""
         t = SogTextures(*[(tex[k].data_ptr() if k in tex else None) for k in
@@ -1324,17 +1403,37 @@ class Context:
             data = f.read()
         return self._read_bytes(data, ksplat_layout, lib().st_ksplat_read, lib().st_dev_ksplat_read, device)
 
-    def read_spz(self, path):
-        """readSpz (read-spz.ts:49-241) -> {name: float32 numpy column}; the gunzip is Python's"""
+    def _read_spz(self, path, device, inflate, chunk_bytes):
+        if inflate not in ('host', 'device'):
+            raise ValueError("inflate must be 'host' or 'device'")
         with open(path, 'rb') as f:
-            data = spz_inflate(f.read())
-        return self._read_bytes(data, spz_layout, lib().st_spz_read, lib().st_dev_spz_read, None)
-
-    def read_spz_dev(self, path, device='cuda'):
-        """readSpz into device columns (torch tensors)"""
-        with open(path, 'rb') as f:
-            data = spz_inflate(f.read())
+            file = f.read()
+        self.last_inflate = 'host'
+        if inflate == 'device':
+            lay = spz_gz_layout(file)
+            if lay is not None:
+                cols, ptrs = self._reader_out(lay[0], lay[1], device)
+                st = InflateStats()
+                read = lib().st_spz_gz_read if device is None else lib().st_dev_spz_gz_read
+                declined = _declined(read(self.h, file, ctypes.c_uint64(len(file)), ptrs, ctypes.c_uint64(chunk_bytes),
+                                          ctypes.byref(st)))
+                self.last_inflate_stats = st.dict()
+                if not declined:
+                    self.last_inflate = 'device'
+                    return cols
+        data = spz_inflate(file)
         return self._read_bytes(data, spz_layout, lib().st_spz_read, lib().st_dev_spz_read, device)
+
+    def read_spz(self, path, inflate='host', chunk_bytes=0):
+        """readSpz (read-spz.ts:49-241) -> {name: float32 numpy column}.  inflate='host': the gunzip is
+        Python's.  inflate='device': the file's bytes go up as they are and the member is inflated in
+        HBM (st_spz_gz_read); a file the device path declines is read the host way, so every accepted
+        file and every error stays as it is.  last_inflate says which way the last read went."""
+        return self._read_spz(path, None, inflate, chunk_bytes)
+
+    def read_spz_dev(self, path, device='cuda', inflate='host', chunk_bytes=0):
+        """readSpz into device columns (torch tensors); `inflate` as for read_spz"""
+        return self._read_spz(path, device, inflate, chunk_bytes)
 
     # ---- the .sog reader (beyond the reference's CLI, which cannot read SOG) --------------------
     def dev_sog_decode(self, meta, count, tex, out):
