@@ -1159,6 +1159,54 @@ int st_spz_gz_read(st_ctx *ctx, const uint8_t *file, uint64_t len, float *const 
 int st_dev_spz_gz_read(st_ctx *ctx, const uint8_t *file, uint64_t len, float *const *cols, uint64_t chunk_bytes,
                        st_inflate_stats *stats);
 
+/* ---- column summary --------------------------------------------------------------------------
+ * What is in a table, column by column: counts, extremes, mean, deviation, median.  The reference
+ * at this version has no such command, so the rules are this project's own, and they are written
+ * so that no result depends on the order of the rows (every writer here reorders them) or on the
+ * shape of a launch: the sum is the real-number sum rounded once, the median is the true order
+ * statistic.  csrc/st_summary.h holds every rule as a host/device function and a serial host form.
+ *
+ * For one column of any st_ply_type, v_i is the element as a JS number (widened exactly).  All
+ * arithmetic is IEEE double, each operation rounds once in the order written, nothing is fused.
+ *   rows       n.  nan_count: the NaN elements, any sign or payload.  inf_count: the +-Infinity
+ *              elements.  m = n - nan_count - inf_count; everything below is over the m finite ones.
+ *   min, max   in the total order in which -0 precedes +0 (Math.min / Math.max).
+ *   sum        the exact real sum, rounded once to double, nearest-even: +-Infinity when its
+ *              magnitude is 2^1024 - 2^970 or more.  No partial sum exists that could leave the
+ *              double range on the way: [1.7e308, 1.7e308, -1.7e308] sums to 1.7e308.
+ *   mean       sum / m, one division, m as a double.  n >= 2^53 is ST_ERR_UNSUPPORTED.
+ *   ssd        d_i = v_i - mean, t_i = d_i * d_i; the exact real sum of the t_i, rounded once;
+ *              +Infinity if any t_i is +Infinity.
+ *   std_dev    sqrt(ssd / m): the population deviation.
+ *   median     the finite elements sorted in the total order above: element (m - 1) / 2 for odd m,
+ *              (a + b) / 2 of elements m / 2 - 1 and m / 2 for even m, computed as written: it may
+ *              overflow, and (-0 + +0) / 2 is +0.
+ *   m = 0      (n = 0 included): min, max, mean, std_dev, median are NaN; sum and ssd are +0.
+ * A table without columns is ST_ERR_ARG.  Columns must be aligned to their type (ST_ERR_ARG, the
+ * message names the column).  Duplicate names are allowed and summarised independently.
+ *
+ * st_dev_summary reads the device columns in place: no column data goes to the host, and the device
+ * scratch is a fixed record per column (the columns go through in batches of 128, one grid
+ * dimension over a batch).  It works on the context stream and waits for it.  st_summary uploads a
+ * host table through the staged copies, about 1 GiB of columns at a time, and runs the same steps.
+ * st_ctx_last_summary_stats: the last call's sum paths as JSON -- {"columns", "fast" (int128 in
+ * units of the column's lowest set bit), "general" (the superaccumulator), "normalisations" (carry
+ * propagations inside a loop), "flush"}.  Switches, read per call: ST_SUM_EXACT=1 sends every
+ * column down the general path; ST_SUM_FLUSH=<n> (1 .. 2^30, the default) is the additions a wave's
+ * accumulator takes between normalisations.
+ * st_summary_text (host only): "column,rows,nanCount,infCount,min,max,mean,stdDev,median\n", then a
+ * line per column: the name as it is (not quoted, as in the CSV writer), the counts as decimal
+ * integers, the doubles as JavaScript prints them (NaN, Infinity, -0 as 0).  malloc'd (st_free);
+ * *size excludes the NUL. */
+typedef struct {
+    uint64_t rows, nan_count, inf_count;
+    double min, max, sum, mean, ssd, std_dev, median;
+} st_col_summary;
+int st_dev_summary(st_ctx *ctx, const st_ttable *dev_table, st_col_summary *out);
+int st_summary(st_ctx *ctx, const st_ttable *host_table, st_col_summary *out);
+int st_summary_text(const st_ttable *t, const st_col_summary *s, char **out, uint64_t *size);
+const char *st_ctx_last_summary_stats(st_ctx *ctx);
+
 #ifdef __cplusplus
 }
 #endif

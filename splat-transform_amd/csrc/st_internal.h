@@ -152,6 +152,8 @@ struct st_ctx {
         uint64_t assigns = 0, points = 0, pairs = 0, ambiguous = 0, overflow = 0, walked_overflow = 0, ties = 0;
     } kn_stats;
     std::string last_kn_stats = "{}";
+    // the last column summary's sum paths (st_ctx_last_summary_stats)
+    std::string last_summary_stats = "{}";
     // kernel profiling (st_ctx_set_profiling)
     bool profiling = false;
     struct KEv {
@@ -485,6 +487,12 @@ bool inflate_dev(st_ctx *c, const uint8_t *dev_in, uint64_t n, uint8_t *dev_out,
                  st_inflate_stats *stats);
 bool gunzip_dev(st_ctx *c, const uint8_t *dev_in, uint64_t n, uint8_t *dev_out, uint64_t expect, uint64_t chunk_bytes,
                 st_inflate_stats *stats);
+
+// the column summary (st_summary.hip; the rules: st_abi.h, "column summary"): one st_col_summary per
+// column of a device table read in place / of a host table uploaded through the staged copies; both
+// wait for the stream and leave the sum paths taken in c->last_summary_stats
+void summary_dev(st_ctx *c, const st_ttable *t, st_col_summary *out);
+void summary_host(st_ctx *c, const st_ttable *t, st_col_summary *out);
 
 // the .ksplat writer (st_ksplat_write.hip; the rules: st_abi.h, "the .ksplat writer").  ksplat_params
 // checks mode, degree (-1: the table's own), block size and harmonics range against a table picked

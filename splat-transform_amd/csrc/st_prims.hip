@@ -570,7 +570,10 @@ void minmax_keys_dev(st_ctx *c, const float *const *cols, int ncols, uint64_t n,
     for (int i = 0; i < ncols; ++i) mc.p[i] = cols[i];
     const unsigned nb = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>(MM_BLOCKS, (n + 4095) / 4096));
     auto *part = wsT<uint32_t>(c, "mm.part", (size_t)ncols * 2 * nb);
-    hipLaunchKernelGGL(k_mm_partial, dim3(nb, ncols), dim3(256), 0, c->stream, mc, n, part);
+    {
+        KTimer kt(c, "mm.partial");
+        hipLaunchKernelGGL(k_mm_partial, dim3(nb, ncols), dim3(256), 0, c->stream, mc, n, part);
+    }
     hipLaunchKernelGGL(k_mm_final, dim3(ncols), dim3(256), 0, c->stream, part, (int)nb, out);
     ST_LAUNCH_CHECK();
 }

@@ -5,6 +5,7 @@ numpy arrays; ``dev_*`` entry points take torch CUDA (HIP) tensors and pass
 their device pointers, running on torch's current stream.  There is no CPU
 fallback: constructing a Context without a gfx950 device raises.
 """
+import collections
 import contextlib
 import ctypes
 import weakref
@@ -140,6 +141,7 @@ EXPORTS = [
     'st_ply_spz_gz_file',
     'st_gzip_member_layout', 'st_inflate_head', 'st_dev_inflate', 'st_dev_gunzip', 'st_spz_gz_layout', 'st_spz_gz_read',
     'st_dev_spz_gz_read',
+    'st_dev_summary', 'st_summary', 'st_summary_text', 'st_ctx_last_summary_stats',
 ]
 
 
@@ -166,6 +168,7 @@ def lib():
         L.st_last_error.restype = ctypes.c_char_p
         L.st_ctx_last_timings.restype = ctypes.c_char_p
         L.st_ctx_last_kmeans_stats.restype = ctypes.c_char_p
+        L.st_ctx_last_summary_stats.restype = ctypes.c_char_p
         L.st_ctx_destroy.restype = None
         L.st_comm_destroy.restype = None
         L.st_group_destroy.restype = None
@@ -183,7 +186,8 @@ def lib():
             getattr(L, name).restype = ctypes.c_uint64
             getattr(L, name).argtypes = [ctypes.c_uint64]
         for name in EXPORTS:
-            if name not in ('st_last_error', 'st_ctx_last_timings', 'st_ctx_last_kmeans_stats', 'st_ctx_destroy', 'st_free', 'st_webp_max_size',
+            if name not in ('st_last_error', 'st_ctx_last_timings', 'st_ctx_last_kmeans_stats',
+                            'st_ctx_last_summary_stats', 'st_ctx_destroy', 'st_free', 'st_webp_max_size',
                             'st_ply_row_bytes', 'st_csv_max_row_bytes', 'st_base64_size', 'st_comm_destroy',
                             'st_group_destroy', 'st_spz_image_size', 'st_ksplat_image_size', 'st_deflate_bound',
                             'st_gzip_bound'):
@@ -597,6 +601,37 @@ def csv_max_row_bytes(cols):
     longest cell plus one separator.  Host only"""
     items = list(cols.items()) if isinstance(cols, dict) else list(cols)
     return lib().st_csv_max_row_bytes(ctypes.byref(_schema_ttable(items, 0)))
+
+
+class ColSummaryC(ctypes.Structure):
+    _fields_ = [('rows', ctypes.c_uint64), ('nan_count', ctypes.c_uint64), ('inf_count', ctypes.c_uint64),
+                ('min', ctypes.c_double), ('max', ctypes.c_double), ('sum', ctypes.c_double),
+                ('mean', ctypes.c_double), ('ssd', ctypes.c_double), ('std_dev', ctypes.c_double),
+                ('median', ctypes.c_double)]
+
+
+ColSummary = collections.namedtuple('ColSummary', [f for f, _ in ColSummaryC._fields_])
+
+
+def _summaries_out(names, raw):
+    """{name: ColSummary}, or a list in column order when a name occurs twice"""
+    vals = [ColSummary(*(getattr(r, f) for f in ColSummary._fields)) for r in raw]
+    return dict(zip(names, vals)) if len(set(names)) == len(names) else vals
+
+
+def summary_text(cols, summaries):
+    """st_summary_text: the header line and one line per column -- name, counts, then min, max, mean,
+    stdDev and median as JavaScript prints them.  cols: a list of (name, anything) or a dict, for the
+    names; summaries: what Context.summary / dev_summary returned (or a list of ColSummary in column
+    order).  Host only -> bytes"""
+    names = [k for k, _ in (cols.items() if isinstance(cols, dict) else cols)]
+    vals = [summaries[k] for k in names] if isinstance(summaries, dict) else list(summaries)
+    assert len(vals) == len(names)
+    raw = (ColSummaryC * max(1, len(names)))(*[ColSummaryC(*v) for v in vals])
+    t = _schema_ttable([(k, np.float32) for k in names], 0)
+    out, size = ctypes.c_void_p(), ctypes.c_uint64(0)
+    check(lib().st_summary_text(ctypes.byref(t), raw, ctypes.byref(out), ctypes.byref(size)))
+    return _take(out, size)
 
 
 def base64_size(nbytes):
@@ -1051,6 +1086,29 @@ class Context:
         """the last N-D k-means' assign classification (st_ctx_last_kmeans_stats) as a dict"""
         import json
         return json.loads(lib().st_ctx_last_kmeans_stats(self.h).decode())
+
+    def _summary(self, fn, cols):
+        t = make_ttable(cols)
+        raw = (ColSummaryC * max(1, t.ncol))()
+        check(fn(self.h, ctypes.byref(t), raw))
+        names = [k for k, _ in (cols.items() if isinstance(cols, dict) else cols)]
+        return _summaries_out(names, raw[:t.ncol])
+
+    def dev_summary(self, cols):
+        """st_dev_summary: the column summary (st_abi.h, "column summary") of device columns (list of
+        (name, tensor) or a dict, any of the eight types) read in place -> {name: ColSummary}; a list
+        in column order when a name occurs twice"""
+        return self._summary(lib().st_dev_summary, cols)
+
+    def summary(self, cols):
+        """st_summary: the same of host columns (numpy arrays), uploaded through the staged copies"""
+        return self._summary(lib().st_summary, cols)
+
+    def summary_stats(self):
+        """the last summary's sum paths (st_ctx_last_summary_stats) as a dict: columns, fast, general,
+        normalisations, flush"""
+        import json
+        return json.loads(lib().st_ctx_last_summary_stats(self.h).decode())
 
     def set_profiling(self, on=True):
         check(lib().st_ctx_set_profiling(self.h, ctypes.c_int32(1 if on else 0)))
