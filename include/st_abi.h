@@ -1207,6 +1207,83 @@ int st_summary(st_ctx *ctx, const st_ttable *host_table, st_col_summary *out);
 int st_summary_text(const st_ttable *t, const st_col_summary *s, char **out, uint64_t *size);
 const char *st_ctx_last_summary_stats(st_ctx *ctx);
 
+/* ---- st_dev_probe: a test hook ----------------------------------------------------------------
+ * The two layers under every bit-exact result, called directly so that tests can compare them
+ * with a reference on inputs of their own choosing: the scalar rules of csrc/st_jsmath.h as
+ * compiled for the device, and the primitives of csrc/st_prims.hip.  No production path calls it
+ * and it adds no kernel to one; the Node addon does not bind it.
+ *
+ * Every pointer in st_probe_args is a device pointer (cols: a host array of device pointers).  The
+ * call works on the context stream and waits for it.  Before any launch it answers ST_ERR_ARG for:
+ * an unknown op; n >= 2^32; a pointer the op needs that is NULL while n > 0, or that is not aligned
+ * to its element type; a bit range outside 0 <= begin_bit <= end_bit <= the key width; ncols
+ * outside 1 .. 64.  Its workspace slots are "probe.*".
+ *
+ * Scalar ops, elementwise over n elements (csrc/st_probe_ops.h holds the expression of each; the
+ * kernel and tests/native/jsmath_cpu_check.cpp both evaluate that one text).  in0 (and in1 for the
+ * two-input ops): float64.  out0: float64, except F32_STORE and F32_CAST (float32), TO_INT32
+ * (int32) and TO_UINT8 (uint8).
+ *   EXP, LOG, SIGMOID, LOG_TRANSFORM   js::exp, js::log, js::sigmoid, js::log_transform
+ *   LOG1ABS                            js::log(|v| + 1)
+ *   LOGEXP                             js::log(js::x86_nan(js::exp(v) * s, v != v || s != s)): the
+ *                                      scale column of transform(), s = args.s
+ *   SQRT, ROUND                        __builtin_sqrt(v), floor(v + 0.5)
+ *   TO_INT32, TO_UINT8, F32_STORE      js::to_int32, js::to_uint8, js::f32_store
+ *   F32_CAST, SIGN                     (float)v, js::sign_
+ *   DIV, MIN, MAX                      in0 / in1, js::min_, js::max_
+ *
+ * Primitive ops: thin calls of the internal functions with the caller's buffers (keys and values
+ * uint32, ST_PROBE_SORT_U64's keys uint64; bits [begin_bit, end_bit) of a key are sorted on).
+ *   SCAN            scan_u32: exclusive scan of in0[0..n) into out0 (may be in0); aux (nullable)
+ *                   receives the total and may be out0 + n
+ *   SORT_U32        radix_sort_u32: out0 (keys) and out1 (values) in place
+ *   SORT_FROM       radix_sort_u32_from: keys in0 (left unchanged), values in1 (NULL: the identity)
+ *                   into out0 / out1, without the fused first histogram.  out0 == in0 or
+ *                   out1 == in1 needs an even pass count: ST_ERR_INTERNAL, nothing written
+ *   SORT_IOTA       radix_sort_u32_iota: in0 -> out0 / out1
+ *   SORT_SWAP       radix_sort_u32_inplace_or_swap on the pair in0 / in1 (overwritten); the pair
+ *                   its returned pointers name is copied to out0 / out1; result = 1 when that pair
+ *                   was in0 / in1, 0 when it was the workspace's
+ *   SORT_U64        radix_sort_u64: out0 (uint64 keys) and out1 in place
+ *   MINMAX          minmax_keys_dev over the ncols float columns cols[0..ncols) of n elements:
+ *                   out0[2a] = min, out0[2a + 1] = max of column a as order-preserving keys
+ *   IOTA            iota_u32: out0[i] = i */
+#define ST_PROBE_EXP 1
+#define ST_PROBE_LOG 2
+#define ST_PROBE_SIGMOID 3
+#define ST_PROBE_LOG_TRANSFORM 4
+#define ST_PROBE_LOG1ABS 5
+#define ST_PROBE_LOGEXP 6
+#define ST_PROBE_SQRT 7
+#define ST_PROBE_ROUND 8
+#define ST_PROBE_TO_INT32 9
+#define ST_PROBE_TO_UINT8 10
+#define ST_PROBE_F32_STORE 11
+#define ST_PROBE_F32_CAST 12
+#define ST_PROBE_SIGN 13
+#define ST_PROBE_DIV 14
+#define ST_PROBE_MIN 15
+#define ST_PROBE_MAX 16
+#define ST_PROBE_SCAN 32
+#define ST_PROBE_SORT_U32 33
+#define ST_PROBE_SORT_FROM 34
+#define ST_PROBE_SORT_IOTA 35
+#define ST_PROBE_SORT_SWAP 36
+#define ST_PROBE_SORT_U64 37
+#define ST_PROBE_MINMAX 38
+#define ST_PROBE_IOTA 39
+typedef struct st_probe_args {
+    void *in0, *in1;
+    void *out0, *out1;
+    void *aux;
+    const float *const *cols;
+    uint64_t n;
+    double s;
+    int32_t begin_bit, end_bit, ncols;
+    int32_t result; /* written by ST_PROBE_SORT_SWAP */
+} st_probe_args;
+int st_dev_probe(st_ctx *ctx, int32_t op, st_probe_args *args);
+
 #ifdef __cplusplus
 }
 #endif

@@ -46,8 +46,9 @@ __host__ __device__ inline uint8_t to_uint8(double v) { return (uint8_t)(to_uint
 __host__ __device__ inline double nan_() { return mkd(0xfff80000u, 0u); }
 // V8 on x86-64: an invalid operation (Inf - Inf, 0 * Inf, 0 / 0, log of a negative) on operands
 // that are not NaN yields the default NaN with the sign bit set (0xFFF8000000000000, 0xFFC00000
-// once stored to a Float32Array); the GPU's default NaN is positive.  A NaN operand propagates on
-// both.  r: an expression's result, nan_in: whether any of its operands was NaN.
+// once stored to a Float32Array); the GPU's default NaN is positive (its division and
+// square-root sequences alone give the negative one, as x86 does: tests/test_probe_scalar_gpu.py).  A NaN operand propagates on both.  r: an expression's result,
+// nan_in: whether any of its operands was NaN.
 __host__ __device__ inline double x86_nan(double r, bool nan_in) { return (r != r && !nan_in) ? nan_() : r; }
 __host__ __device__ inline float x86_nanf(float r, bool nan_in) {
     return (r != r && !nan_in) ? __builtin_bit_cast(float, 0xffc00000u) : r;

@@ -142,6 +142,7 @@ EXPORTS = [
     'st_gzip_member_layout', 'st_inflate_head', 'st_dev_inflate', 'st_dev_gunzip', 'st_spz_gz_layout', 'st_spz_gz_read',
     'st_dev_spz_gz_read',
     'st_dev_summary', 'st_summary', 'st_summary_text', 'st_ctx_last_summary_stats',
+    'st_dev_probe',
 ]
 
 
@@ -611,6 +612,20 @@ class ColSummaryC(ctypes.Structure):
 
 
 ColSummary = collections.namedtuple('ColSummary', [f for f, _ in ColSummaryC._fields_])
+
+
+class ProbeArgs(ctypes.Structure):
+    _fields_ = [('in0', ctypes.c_void_p), ('in1', ctypes.c_void_p), ('out0', ctypes.c_void_p), ('out1', ctypes.c_void_p),
+                ('aux', ctypes.c_void_p), ('cols', ctypes.c_void_p), ('n', ctypes.c_uint64), ('s', ctypes.c_double),
+                ('begin_bit', ctypes.c_int32), ('end_bit', ctypes.c_int32), ('ncols', ctypes.c_int32),
+                ('result', ctypes.c_int32)]
+
+
+# st_abi.h's ST_PROBE_* codes
+PROBE_OPS = {'exp': 1, 'log': 2, 'sigmoid': 3, 'log_transform': 4, 'log1abs': 5, 'logexp': 6, 'sqrt': 7, 'round': 8,
+             'to_int32': 9, 'to_uint8': 10, 'f32_store': 11, 'f32_cast': 12, 'sign': 13, 'div': 14, 'min': 15, 'max': 16,
+             'scan': 32, 'sort_u32': 33, 'sort_from': 34, 'sort_iota': 35, 'sort_swap': 36, 'sort_u64': 37,
+             'minmax': 38, 'iota': 39}
 
 
 def _summaries_out(names, raw):
@@ -1109,6 +1124,21 @@ class Context:
         normalisations, flush"""
         import json
         return json.loads(lib().st_ctx_last_summary_stats(self.h).decode())
+
+    def dev_probe(self, op, in0=None, in1=None, out0=None, out1=None, aux=None, cols=None, n=0, s=0.0,
+                  begin_bit=0, end_bit=0):
+        """st_dev_probe, a test hook (st_abi.h): one of PROBE_OPS by name or code over device tensors
+        (or raw device addresses); cols: the float32 column tensors of 'minmax'.  Returns args.result
+        (1 when 'sort_swap' left the result in the caller's pair)"""
+        def p(t):
+            return ctypes.c_void_p(t) if isinstance(t, int) else _ptr(t)
+        a = ProbeArgs(p(in0), p(in1), p(out0), p(out1), p(aux), None, n, s, begin_bit, end_bit, 0, 0)
+        if cols is not None:
+            a.ncols = len(cols)
+            ptrs = (ctypes.c_void_p * max(1, len(cols)))(*[p(t) for t in cols])
+            a.cols = ctypes.cast(ptrs, ctypes.c_void_p)
+        check(lib().st_dev_probe(self.h, ctypes.c_int32(PROBE_OPS.get(op, op)), ctypes.byref(a)))
+        return a.result
 
     def set_profiling(self, on=True):
         check(lib().st_ctx_set_profiling(self.h, ctypes.c_int32(1 if on else 0)))
