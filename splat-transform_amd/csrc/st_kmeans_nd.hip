@@ -14,7 +14,9 @@
 // with e_abs = 2^-25 when the matrix cores keep fp16 denormals (probed once per
 // context) and 2^-14 otherwise.  The epilogue keeps, per point and lane-half, the
 // running top-3 of the 16-row tile minima (a v_min3 tree per tile, then two v_med3 +
-// one v_min) and the tiles of the best two.  m2 > m1 + W_p (W_p = 2E + 2 delta_p,
+// one v_min, run only where the tile's minimum is below the lane's guard of its third-best:
+// about 1% of the lane-slots at K = 65,536; ST_SWEEP_UPDATE picks the unguarded form)
+// and the tiles of the best two.  m2 > m1 + W_p (W_p = 2E + 2 delta_p,
 // delta_p = the reference's own f64 rounding) decides the point: k_fixrow finds the
 // row inside the best tile-half with the exact f64 distance.  m3 > m1 + W_p puts
 // every candidate in the best two tile-halves: k_fixpair settles those 32 rows.
@@ -30,6 +32,7 @@
 // layout puts the point on the lane (col = lane & 31) and 16 centroid rows per
 // lane-half in registers, so the top-3 update is lane-local.
 #include <cmath>
+#include <cstring>
 #include <utility>
 
 #include "st_kmeans.h"
@@ -57,6 +60,11 @@ constexpr int PT = 4;          // point tiles per wave
 constexpr int NW = 4;          // waves per workgroup (they share the LDS centroid stages)
 constexpr int WG = 64 * NW;    // threads per workgroup
 constexpr int CT_STAGE = 8;    // centroid tiles per LDS stage
+// the main sweep's running top-3 update: every slot in every lane, or only where a slot's minimum
+// can enter a lane's top-3 -- a per-lane branch (EXEC masked on every slot), a wave-uniform skip
+// around the unmasked update, or the skip around the per-lane branch (the fall-through of a slot
+// is then one compare and one s_cbranch_vccz).  All four give the same bits.
+enum { UPD_ALWAYS = 0, UPD_LANE = 1, UPD_WAVE = 2, UPD_BOTH = 3, UPD_DEFAULT = UPD_BOTH };
 constexpr int CAND_CAP = 64;   // candidate slots per ambiguous point
 constexpr int CAND_CAP2 = 2048;  // ... per point whose list overflowed (a second collect)
 constexpr int OVF_BATCH = 4096;  // overflowed points per second collect (32 MiB of lists, kept by the workspace)
@@ -65,6 +73,17 @@ constexpr int OVF_BATCH = 4096;  // overflowed points per second collect (32 MiB
 uint32_t sumnd_big() {
     const char *e = getenv("ST_SUMND_BIG");  // read per call (tests set it around one call)
     return e ? (uint32_t)std::max(1ul, strtoul(e, nullptr, 10)) : 16384u;
+}
+
+// ST_SWEEP_UPDATE=always|lane|wave|both picks the main sweep's top-3 update (A/B in one build, tests)
+int sweep_update() {
+    const char *e = getenv("ST_SWEEP_UPDATE");  // read per call (tests set it around one call)
+    if (!e || !*e) return UPD_DEFAULT;
+    if (!strcmp(e, "always")) return UPD_ALWAYS;
+    if (!strcmp(e, "lane")) return UPD_LANE;
+    if (!strcmp(e, "wave")) return UPD_WAVE;
+    if (!strcmp(e, "both")) return UPD_BOTH;
+    throw Error(ST_ERR_UNSUPPORTED, "ST_SWEEP_UPDATE: always, lane, wave or both");
 }
 
 __host__ __device__ inline int kp_of(int d) { return ((d + 3) + 15) / 16 * 16; }
@@ -419,9 +438,12 @@ __global__ __launch_bounds__(64 * CF_W) void k_centroid_frags(const float *cen, 
 // Software pipeline over "slots" (one centroid tile x one point tile = KS MFMAs): the
 // epilogue of the previous slot is cut into KS slices, slice s issued right behind
 // MFMA s of this slot and fenced with sched_barrier, so each MFMA's 32 cycles on the
-// matrix pipe cover ~10 VALU ops of the same wave.  Occupancy is 3 waves per SIMD (160 VGPRs:
-// B fragments 48, score buffers 64, A ping-pong 24, top-3 state; 48 KiB of LDS per workgroup).
-template <int KS, int MODE>
+// matrix pipe cover ~10 VALU ops of the same wave.  Occupancy is 3 waves per SIMD (160 VGPRs,
+// 164 with the guarded update: B fragments 48, score buffers 64, A ping-pong 24, top-3 state and
+// its guard; 48 KiB of LDS per workgroup).  UPD (MODE 0): how the last slice of a slot updates the
+// running top-3 -- see the enum; the sweep is power-limited, so the lane-work a guard saves
+// comes back as clock.
+template <int KS, int MODE, int UPD = UPD_ALWAYS>
 __global__ __launch_bounds__(WG) void k_sweep(const uint4 *__restrict__ pfrag, uint32_t ntiles, uint32_t npts,
                                                const uint4 *__restrict__ cfrag, uint32_t ctiles,
                                                const float *__restrict__ pnorm, const float *__restrict__ pdn,
@@ -456,10 +478,26 @@ __global__ __launch_bounds__(WG) void k_sweep(const uint4 *__restrict__ pfrag, u
     asm volatile("v_mov_b32 %0, 0xff800000" : "=v"(ninf));
     // per point tile: top-3 of the keyed tile minima seen by this lane-half (key = the tile
     // minimum with the tile index in its low kbits mantissa bits)
-    float m1[PT], m2[PT], m3[PT], th[PT];
-    bool full[PT];  // MODE 1: this lane saw its point's candidate list overflow
     const uint32_t kbits = ctiles > 1 ? 32u - (uint32_t)__builtin_clz(ctiles - 1) : 0u;
     const uint32_t kmask = (1u << kbits) - 1u;
+    float m1[PT], m2[PT], m3[PT], th[PT];
+    // the guarded forms' threshold m3u.  A slot changes the top-3 only when key < m3, and
+    // that implies mn < m3u with m3u = m3 + 4 dk |m3| + 2^-126, dk = 2^(kbits - 23): key and mn
+    // share sign and binade and differ by < 2^kbits ulp, so mn <= key + dk |key| + kd, kd =
+    // 2^(kbits - 149) for the denormal binade (the keys of a zero minimum; f32 denormals are
+    // kept, as the keys' own order needs).  For key < m3:
+    //   0 <= key:       mn <= key (1 + dk) + kd < m3 (1 + dk) + kd
+    //   key < 0 <= m3:  mn <= -0 <= m3 < m3 + kd
+    //   key < m3 < 0:   mn <= key (1 - dk) + kd < m3 (1 - dk) + kd = m3 + dk |m3| + kd
+    // so mn < m3 + dk |m3| + kd throughout.  The two f32 roundings of m3u lose at most
+    // 2^-23 (1 + 4 dk) |m3| + 2^-23 2^-126 <= 2 dk |m3| + 2^-149 (dk >= 2^-23, 4 dk <= 1 for
+    // kbits <= 21; an underflowing product loses < 2^-149 more), which leaves m3u >= m3 +
+    // 2 dk |m3| + 2^-127 above it.  m3 = +inf gives m3u = +inf.  When the guard fails, key >= m3
+    // and the update would write back m1, m2, m3 as they are: the result is the unguarded one.
+    float m3u[PT];
+    const float gdk = __builtin_ldexpf(1.0f, (int)kbits - 21);
+    auto guard_of = [&](float m) { return __builtin_fmaf(__builtin_fabsf(m), gdk, m) + 0x1p-126f; };
+    bool full[PT];  // MODE 1: this lane saw its point's candidate list overflow
     uint32_t kmask_v;  // in a VGPR: v_bfi_b32 takes one scalar operand (the tile index)
     asm volatile("v_mov_b32 %0, %1" : "=v"(kmask_v) : "s"(kmask));
 #pragma unroll
@@ -467,6 +505,7 @@ __global__ __launch_bounds__(WG) void k_sweep(const uint4 *__restrict__ pfrag, u
         m1[t] = __builtin_inff();
         m2[t] = __builtin_inff();
         m3[t] = __builtin_inff();
+        m3u[t] = __builtin_inff();
         th[t] = -__builtin_inff();
         full[t] = false;
         if (MODE == 1) {
@@ -488,14 +527,40 @@ __global__ __launch_bounds__(WG) void k_sweep(const uint4 *__restrict__ pfrag, u
         for (int r = (q == 0 ? 1 : r0); r < r1; ++r) mn = fminf(mn, sc[r]);
         if (q == KS - 1) {
             if (MODE == 0) {
-                // branch-free top-3: the tile index rides in the key's low kbits bits (v_bfi;
+                // top-3 without compares: the tile index rides in the key's low kbits bits (v_bfi;
                 // |key - mn| < 2^kbits ulp, added to the decision window), two v_med3 + one v_min
-                uint32_t kb;
-                asm("v_bfi_b32 %0, %1, %2, %3" : "=v"(kb) : "v"(kmask_v), "s"(ctile), "v"(mn));
-                const float key = __builtin_bit_cast(float, kb);
-                m3[t] = __builtin_amdgcn_fmed3f(m2[t], m3[t], key);
-                m2[t] = __builtin_amdgcn_fmed3f(m1[t], m2[t], key);
-                m1[t] = fminf(m1[t], key);
+                auto update = [&] {
+                    uint32_t kb;
+                    asm("v_bfi_b32 %0, %1, %2, %3" : "=v"(kb) : "v"(kmask_v), "s"(ctile), "v"(mn));
+                    const float key = __builtin_bit_cast(float, kb);
+                    m3[t] = __builtin_amdgcn_fmed3f(m2[t], m3[t], key);
+                    m2[t] = __builtin_amdgcn_fmed3f(m1[t], m2[t], key);
+                    m1[t] = fminf(m1[t], key);
+                };
+                // guarded forms: the fall-through of a slot is the min tree and one compare (the
+                // v_bfi asm keeps the compiler from turning the branch into selects)
+                if (UPD == UPD_ALWAYS) {
+                    update();
+                } else if (UPD == UPD_WAVE) {
+                    if (__ballot(mn < m3u[t]) != 0) {
+                        update();
+                        m3u[t] = guard_of(m3[t]);
+                    }
+                } else if (UPD == UPD_LANE) {
+                    if (mn < m3u[t]) {
+                        update();
+                        m3u[t] = guard_of(m3[t]);
+                    }
+                } else {  // UPD_BOTH: the wave-uniform skip around the per-lane branch
+                    const bool below = mn < m3u[t];
+                    if (__ballot(below) != 0) {
+                        asm volatile("");  // keeps the two branches apart
+                        if (below) {
+                            update();
+                            m3u[t] = guard_of(m3[t]);
+                        }
+                    }
+                }
             } else if (mn <= th[t] && !full[t]) {
                 // candidates are rare (a handful of the K centroids per point); once the point's
                 // list has overflowed (coinciding centroids: thousands of candidates) this lane
@@ -2094,10 +2159,17 @@ struct Sweep {
         const uint32_t per_block = NW * PT;
         const dim3 grid((ntiles + per_block - 1) / per_block);
         KTimer kt(c, "kn.sweep");
-        hipLaunchKernelGGL((k_sweep<KS, 0>), grid, dim3(WG), 0, c->stream, pfrag, ntiles, n, cfrag, ctiles, pnorm,
-                           pdn, cmax, chalf, chalf_d, ntab, bnd, labels, thr, amb, st, (uint32_t *)nullptr, (uint32_t *)nullptr, 0u,
-                           pair_pts,
-                           pair_codes, code_hist);
+        auto launch = [&](auto kernel) {
+            hipLaunchKernelGGL(kernel, grid, dim3(WG), 0, c->stream, pfrag, ntiles, n, cfrag, ctiles, pnorm, pdn,
+                               cmax, chalf, chalf_d, ntab, bnd, labels, thr, amb, st, (uint32_t *)nullptr,
+                               (uint32_t *)nullptr, 0u, pair_pts, pair_codes, code_hist);
+        };
+        switch (sweep_update()) {
+            case UPD_LANE: launch(k_sweep<KS, 0, UPD_LANE>); break;
+            case UPD_WAVE: launch(k_sweep<KS, 0, UPD_WAVE>); break;
+            case UPD_BOTH: launch(k_sweep<KS, 0, UPD_BOTH>); break;
+            default: launch(k_sweep<KS, 0, UPD_ALWAYS>); break;
+        }
         ST_LAUNCH_CHECK();
     }
     static void collect(st_ctx *c, const uint4 *afrag, uint32_t atiles, uint32_t namb, const uint4 *cfrag,
