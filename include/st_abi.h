@@ -572,7 +572,15 @@ int st_ply_read(st_ctx *ctx, int32_t fd, const st_ply_header *h, int32_t element
  * writeSog host forms (st_sog, st_sog_bundle, st_sog_file) given a lazy column run on its device
  * copy directly; every other host form copies it down first.  Each lazy column holds a device
  * block of its own until it is materialized or st_ply_forget-ten (later reads do not touch it);
- * the caller keeps the host column alive until then. */
+ * the caller keeps the host column alive until then.
+ * A lazy column belongs to the context that read it.  Any other context, and an explicit group
+ * (st_group_sog*), refuses a table that holds one, or a view of one, with ST_ERR_ARG and writes
+ * nothing: st_ply_materialize it on its own context first.  The default group (st_set_devices,
+ * ST_NUM_GPUS) is given host bytes, so st_sog / st_sog_bundle / st_sog_file copy the caller
+ * context's lazy columns down before its ranks upload them (st_ctx_last_host_reuse: 0, 0).
+ * A host form that overwrites a lazy column whole drops its device copy without copying; one that
+ * overwrites only part of it (a view) copies the column down first, so the other rows keep the
+ * read's values. */
 int st_ply_read_resident(st_ctx *ctx, int32_t fd, const st_ply_header *h, int32_t element, void *const *host_cols);
 /* a lazy column's values copied into its host memory (then an ordinary host column: the caller
  * may change it); no-op for any other pointer */

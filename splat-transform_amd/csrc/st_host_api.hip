@@ -186,7 +186,8 @@ bool resident_table(st_ctx *c, const st_table *h, const std::vector<std::string>
         std::vector<HostXfer> v;
         v.swap(up.v);
         // (the lock is held: staged_h2d's own bookkeeping would take it again, and these sources are
-        // not lazy -- the lazy ones are read on the device)
+        // not lazy -- the lazy ones are read on the device; another context's are refused)
+        refuse_foreign_lazy(c, v);
         staged_h2d_raw(c, v);
     }
     for (auto &s : d.names) d.cnames.push_back(s.c_str());
@@ -303,6 +304,14 @@ void host_sog(st_ctx *c, const st_table *t, int iters, const double *draws, uint
         if (file) {
             ST_ARG(to.size, bad);
             sog_file_check(to.fd);
+        }
+        if (c) {  // the ranks' contexts know nothing of c's resident columns: they upload host bytes
+            ST_ARG(t && (t->ncol == 0 || t->cols), "NULL argument");
+            use_device(c);
+            std::vector<HostXfer> read;  // as materialize_lazy, and a view of a lazy column brings it down too
+            for (int i = 0; i < t->ncol; ++i) read.push_back(HostXfer{t->cols[i], nullptr, t->n * sizeof(float)});
+            mirrors_before_h2d(c, read);
+            c->last_reuse_cols = c->last_reuse_bytes = 0;
         }
         return group_sog_to(g.get(), &t, 1, nullptr, nullptr, nullptr, iters, draws, ndraws, used, to);
     }

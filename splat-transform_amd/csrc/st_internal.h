@@ -180,7 +180,8 @@ struct st_ctx {
     //    block of the mirror's own (`dev_bytes`), until st_ply_materialize copies them down (the
     //    mirror is then dropped: the caller may change them).  The writeSog host forms read `dev`
     //    directly; every other host form materializes first (the staged copies' bookkeeping).
-    //    st_ply_forget drops one whose host memory goes away.  A dropped mirror's block goes to
+    //    Only this context can: every lazy range is also in the process-wide record (lazy_range_add),
+    //    and another context's upload of one is refused.  st_ply_forget drops one whose host memory goes away.  A dropped mirror's block goes to
     //    dev_pool for the next resident read's columns of the same size (freed with the context).
     // mirror_mu guards the list and the pool (the Node addon's finalizers call st_ply_forget from
     // any thread).
@@ -240,7 +241,8 @@ inline void *ws_upload(st_ctx *c, const std::string &slot, const void *host, siz
 void staged_h2d_raw(st_ctx *c, const std::vector<HostXfer> &xs);  // without the mirrors' bookkeeping
 void staged_d2h_raw(st_ctx *c, const std::vector<HostXfer> &xs);  // without the mirrors' bookkeeping
 // st_ctx::HostMirror bookkeeping of the staged copies (st_ply.hip): lazy sources are copied down
-// before an upload reads them; overwritten destinations stop being mirrors
+// before an upload reads them; overwritten destinations stop being mirrors (a lazy one that is
+// only partly overwritten is copied down first: its other rows exist nowhere else)
 void mirrors_before_h2d(st_ctx *c, const std::vector<HostXfer> &xs);
 void mirrors_before_d2h(st_ctx *c, const std::vector<HostXfer> &xs);
 // host-side copy over the context's copy threads (large copies split; small ones inline)
@@ -405,6 +407,16 @@ void ply_read_host(st_ctx *c, int fd, const st_ply_header &h, int element, void 
 void materialize_lazy(st_ctx *c, const void *const *host, int n);
 // (mirror_mu held) the mirrors `pick` selects removed, their own device blocks pooled
 void drop_mirrors_locked(st_ctx *c, const std::function<bool(const st_ctx::HostMirror &)> &pick);
+// the process-wide record of lazy host ranges (address, bytes, owning context; one mutex, taken
+// after a context's mirror_mu where both are held): a lazy column is unfilled memory to every
+// context but the one that read it.  Added where ply_read_host registers lazy mirrors, removed by
+// drop_mirrors_locked and st_ctx_destroy.
+void lazy_range_add(st_ctx *c, const void *host, uint64_t bytes);
+void lazy_range_remove(st_ctx *c, const void *host);
+void lazy_ranges_forget(st_ctx *c);
+// ST_ERR_ARG when an upload's source overlaps a lazy range of a context other than c (staged_h2d
+// after c's own mirrors came down, resident_table's uploads; not staged_h2d_raw itself)
+void refuse_foreign_lazy(st_ctx *c, const std::vector<HostXfer> &xs);
 void decompress_ply_dev(st_ctx *c, uint64_t n, const float *const *chunk, const uint32_t *const *vertex,
                         const uint8_t *const *sh, int nsh, float *const *out);
 // the PLY writer (write-ply.ts): k_ply_rows over one device table, the inverse of the reader's

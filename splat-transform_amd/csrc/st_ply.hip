@@ -735,8 +735,58 @@ void drop_mirrors_locked(st_ctx *c, const std::function<bool(const st_ctx::HostM
             continue;
         }
         if (m.dev_bytes) c->dev_pool.emplace_back(const_cast<void *>(m.dev), m.dev_bytes);
+        if (m.lazy) lazy_range_remove(c, m.host);
     }
     c->mirrors.swap(keep);
+}
+
+namespace {
+struct LazyRange {
+    const char *host;
+    uint64_t bytes;
+    st_ctx *owner;
+};
+std::mutex g_lazy_mu;
+std::vector<LazyRange> g_lazy;
+std::atomic<size_t> g_lazy_count{0};  // g_lazy.size(): an upload skips the lock while nothing is lazy
+}  // namespace
+
+void lazy_range_add(st_ctx *c, const void *host, uint64_t bytes) {
+    std::lock_guard<std::mutex> lk(g_lazy_mu);
+    g_lazy.push_back({static_cast<const char *>(host), bytes, c});
+    g_lazy_count.store(g_lazy.size());
+}
+
+void lazy_range_remove(st_ctx *c, const void *host) {
+    std::lock_guard<std::mutex> lk(g_lazy_mu);
+    for (size_t i = 0; i < g_lazy.size(); ++i)
+        if (g_lazy[i].owner == c && g_lazy[i].host == host) {
+            g_lazy.erase(g_lazy.begin() + (long)i);
+            break;
+        }
+    g_lazy_count.store(g_lazy.size());
+}
+
+void lazy_ranges_forget(st_ctx *c) {
+    std::lock_guard<std::mutex> lk(g_lazy_mu);
+    g_lazy.erase(std::remove_if(g_lazy.begin(), g_lazy.end(), [&](const LazyRange &r) { return r.owner == c; }),
+                 g_lazy.end());
+    g_lazy_count.store(g_lazy.size());
+}
+
+void refuse_foreign_lazy(st_ctx *c, const std::vector<HostXfer> &xs) {
+    if (!g_lazy_count.load()) return;
+    std::lock_guard<std::mutex> lk(g_lazy_mu);
+    for (const auto &r : g_lazy) {
+        if (r.owner == c) continue;
+        for (const auto &x : xs) {
+            const char *b = static_cast<const char *>(x.host);
+            if (x.bytes && r.bytes && b < r.host + r.bytes && r.host < b + x.bytes)
+                throw Error(ST_ERR_ARG,
+                            "host column is resident in another context (st_ply_read_resident left it unfilled): "
+                            "only the context that read it can use it; st_ply_materialize it there first");
+        }
+    }
 }
 
 // (mirror_mu held) a device block of `bytes` for a resident column: a pooled one of that size, or
@@ -786,15 +836,31 @@ void mirrors_before_h2d(st_ctx *c, const std::vector<HostXfer> &xs) {
 }
 
 // staged_d2h's destinations: a host column about to be overwritten is no longer its device copy's
-// mirror (lazy or not: dropped without copying)
+// mirror: dropped without copying when one destination covers it whole.  A lazy column that is
+// only partly overwritten is copied down first (its other rows exist nowhere else; the copies
+// into the overwritten part follow on the same stream)
 void mirrors_before_d2h(st_ctx *c, const std::vector<HostXfer> &xs) {
     std::lock_guard<std::mutex> lk(c->mirror_mu);
     if (c->mirrors.empty()) return;
-    drop_mirrors_locked(c, [&](const st_ctx::HostMirror &m) {
+    auto hit = [&](const st_ctx::HostMirror &m) {
         for (const auto &x : xs)
             if (overlaps(m, x.host, x.bytes)) return true;
         return false;
-    });
+    };
+    auto covered = [&](const st_ctx::HostMirror &m) {
+        const char *a = static_cast<const char *>(m.host);
+        for (const auto &x : xs) {
+            const char *b = static_cast<const char *>(x.host);
+            if (b <= a && a + m.bytes <= b + x.bytes) return true;
+        }
+        return false;
+    };
+    std::vector<HostXfer> rest;
+    for (const auto &m : c->mirrors)
+        if (m.lazy && hit(m) && !covered(m))
+            rest.push_back(HostXfer{const_cast<void *>(m.host), const_cast<void *>(m.dev), (size_t)m.bytes});
+    if (!rest.empty()) staged_d2h_raw(c, rest);
+    drop_mirrors_locked(c, hit);
 }
 
 void ply_read_host(st_ctx *c, int fd, const st_ply_header &h, int element, void *const *host_cols, bool lazy) {
@@ -844,8 +910,10 @@ void ply_read_host(st_ctx *c, int fd, const st_ply_header &h, int element, void 
             return false;
         });
         if (el.count)  // (an empty element has nothing to keep)
-            for (int p = 0; p < np; ++p)
+            for (int p = 0; p < np; ++p) {
                 c->mirrors.push_back({host_cols[p], el.count * P.sz[p], nullptr, dcols[p], element, true, dbytes[p]});
+                lazy_range_add(c, host_cols[p], el.count * P.sz[p]);
+            }
         return;
     }
     // an eager read overwrites this element's device slots and the shared host twins: every other

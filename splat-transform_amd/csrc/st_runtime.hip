@@ -220,6 +220,7 @@ struct XferLog {
 
 void staged_h2d(st_ctx *c, const std::vector<HostXfer> &xs) {
     mirrors_before_h2d(c, xs);
+    refuse_foreign_lazy(c, xs);  // what is still lazy belongs to another context
     staged_h2d_raw(c, xs);
 }
 
@@ -427,6 +428,7 @@ void st_ctx_destroy(st_ctx *c) {
     if (c->archive) (void)hipHostFree(c->archive);
     if (c->io) (void)hipHostFree(c->io);
     std::free(c->shadow);
+    lazy_ranges_forget(c);
     for (auto &m : c->mirrors)
         if (m.dev_bytes) (void)hipFree(const_cast<void *>(m.dev));
     for (auto &b : c->dev_pool) (void)hipFree(b.first);

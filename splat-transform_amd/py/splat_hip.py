@@ -1303,7 +1303,11 @@ class Context:
         """readPly (read-ply.ts:111-191) -> (comments, [(element, {prop: numpy column})]); rows go through HBM.
         resident: st_ply_read_resident -- the numpy columns stay unfilled (the values live in HBM) until
         materialize(column) or a host form other than writeSog's reads them; keep them alive until then,
-        or forget() them"""
+        or forget() them.  They belong to this context: another Context and an explicit Group refuse
+        them (StError, ST_ERR_ARG) until this one has materialized them; the default group's writeSog
+        copies them down first.  A form that overwrites a whole column drops its device copy; one
+        that overwrites part of it (a slice) copies the column down first, so the other rows keep the
+        read's values"""
         with _ply_in(path) as (fd, h):
             out = []
             read = lib().st_ply_read_resident if resident else lib().st_ply_read

@@ -284,3 +284,43 @@ def test_js_resident_read_columns_through_write_sog_file(addon_built, tmp_path):
     assert np.array_equal(got.view(np.uint32), cols['f_rest_44'].view(np.uint32))
     got = np.fromfile(tmp_path / 'meta_x.bin', np.float32)
     assert np.array_equal(got.view(np.uint32), cols['x'].view(np.uint32))
+
+
+@pytest.mark.gpu
+def test_js_resident_read_on_the_default_group_equals_the_eager_read(addon_built, tmp_path):
+    """the default group (ST_DEFAULT_GROUP_RANKS=2: two host-staged ranks) uploads host bytes, so
+    writeSogFile / writeSogBundle copy the resident columns down first (host_sog's group branch):
+    every archive of tests/js/resident_read.js equals the same run on eager reads
+    (ST_READ_RESIDENT=0), and the untouched table's equals the one-device run's"""
+    sys.path.insert(0, ROOT)
+    import bench
+    n = 30_011
+    cols = {k: v.numpy() for k, v in bench.synth_table(n, 4243, 'cpu').items()}
+    src = tmp_path / 'in.ply'
+    head = ('ply\nformat binary_little_endian 1.0\n' + f'element vertex {n}\n' +
+            ''.join(f'property float {k}\n' for k in bench.PLY_ORDER) + 'end_header\n').encode()
+    rows = np.stack([cols[k] if k in cols else np.zeros(n, np.float32) for k in bench.PLY_ORDER], 1)
+    src.write_bytes(head + rows.astype('<f4').tobytes())
+    out = {}
+    for name, extra in (('group', dict(ST_DEFAULT_GROUP_RANKS='2')),
+                        ('group_eager', dict(ST_DEFAULT_GROUP_RANKS='2', ST_READ_RESIDENT='0')),
+                        ('one', dict(ST_DEFAULT_GROUP_RANKS=''))):
+        d = tmp_path / name
+        d.mkdir()
+        env = dict(os.environ, **extra)
+        env.pop('ST_NUM_GPUS', None)
+        if 'ST_READ_RESIDENT' not in extra:
+            env.pop('ST_READ_RESIDENT', None)
+        r = subprocess.run([NODE, os.path.join(ROOT, 'tests', 'js', 'resident_read.js'), str(src), str(d), '2'],
+                           capture_output=True, text=True, timeout=600, env=env)
+        assert r.returncode == 0, name + r.stdout + r.stderr
+        out[name] = json.loads(r.stdout.strip().splitlines()[-1])
+    for case in ('untouched', 'read', 'changed', 'changed_ref', 'first', 'second', 'bundle', 'meta'):
+        assert out['group'][case]['sha'] == out['group_eager'][case]['sha'], (case, out)
+        assert out['group'][case]['reused'] == 0, (case, out)  # the ranks upload: nothing runs from HBM
+    assert out['one']['untouched']['reused'] == 59, out
+    assert out['group']['untouched']['sha'] == out['one']['untouched']['sha'], out
+    assert out['group']['numRows'] == n and out['group']['columns'] == 62, out
+    for name in ('group', 'group_eager'):
+        got = np.fromfile(tmp_path / name / 'first_f_rest_44.bin', np.float32)
+        assert np.array_equal(got.view(np.uint32), cols['f_rest_44'].view(np.uint32)), name
