@@ -16,8 +16,9 @@
 // global order: the whole shard for N-D k-means, one column of the shard for
 // cluster1d's column-major concatenation (write-sog.ts:56-99).
 //
-// The caller (splat-transform_amd/py/splat_dist.py) runs the collectives with
-// torch.distributed (RCCL over xGMI, or gloo) between these calls.
+// Two callers run the collectives between these calls: splat_dist.py (one
+// process per GPU, torch.distributed: RCCL over xGMI, or gloo) through the
+// st_dev_kmeans_* step API, and kmeans_sharded (st_multi.hip) directly.
 #include <cmath>
 
 #include "st_jsmath.h"
@@ -27,7 +28,6 @@ namespace st {
 namespace {
 
 using namespace km;
-
 
 // sort key of point i: (segment, label)
 // (n < 2^31: 32-bit index arithmetic; the segment of i advances by a compare, not a division)
@@ -206,35 +206,44 @@ void dist_assign(st_ctx *c, const float *const *cols, int d, uint64_t n, int k, 
     nd_assign(c, dcols, d, n, k, cen, labels, dstate);
 }
 
+namespace {
+
+// The context's record of the last partials (kept for dist_seqsum), set whole: every site
+// states every field.  pts (1-D) and labels: what a member order that was not built
+// (sorted = false) is built from if a pending pair needs it, null where it was.
+void set_last_partials(st_ctx *c, int nseg, int k, int d, uint64_t n, const float *pts, const uint32_t *labels,
+                       bool sorted) {
+    c->ds_nseg = nseg;
+    c->ds_k = k;
+    c->ds_d = d;
+    c->ds_n = n;
+    c->ds_pts = pts;
+    c->ds_labels = labels;
+    c->ds_sorted = sorted;
+}
+
+// the (segment, label) member order of a shard by a radix sort: payload = the members' value
+// bits (vals: the 1-D column) or point indices (vals null: N-D), start = the nseg * k ranges
+void member_order(st_ctx *c, const uint32_t *labels, uint64_t n, int nseg, int k, const float *vals, uint32_t *payload,
+                  uint32_t *start) {
+    const uint64_t nk = (uint64_t)nseg * k;
+    auto *keys = wsT<uint32_t>(c, "ds.keys", n);
+    hipLaunchKernelGGL(k_seg_keys, dim3(grid_for(n, 256, 8192)), dim3(256), 0, c->stream, labels, (uint32_t)n,
+                       (uint32_t)(n / nseg), k, vals, keys, payload);
+    ST_LAUNCH_CHECK();
+    radix_sort_u32(c, keys, payload, n, 0, label_bits(nk), "ds.sort");
+    bounds_from_sorted(c, keys, n, (int)nk, start);
+}
+
+}  // namespace
+
 void dist_assign_partials1d(st_ctx *c, const float *pts, uint64_t n, int nseg, int k, const float *cen,
                             uint32_t *labels, double *sums, double *sabs, int32_t *emin, uint32_t *counts) {
     ST_REQUIRE(n < (1ull << 31) && (uint64_t)nseg * k < (1ull << 31), ST_ERR_ARG, "kmeans partials: too large");
     assign_partials1d(c, pts, n, nseg, k, cen, labels, sums, sabs, emin, counts);
-    c->ds_nseg = nseg;
-    c->ds_k = k;
-    c->ds_d = 1;
-    c->ds_n = n;
-    c->ds_pts = pts;
-    c->ds_labels = labels;
-    c->ds_sorted = false;
+    // the member order is built only if a pending pair needs it
+    set_last_partials(c, nseg, k, 1, n, pts, labels, false);
 }
-
-namespace {
-// the (segment, label) member order of an N-D shard: payload = point indices, start = ranges
-void member_order_nd(st_ctx *c, const uint32_t *labels, uint64_t n, int nseg, int k) {
-    const uint64_t nk = (uint64_t)nseg * k;
-    auto *keys = wsT<uint32_t>(c, "ds.keys", n);
-    auto *payload = wsT<uint32_t>(c, "ds.payload", n);
-    auto *start = wsT<uint32_t>(c, "ds.start", nk + 1);
-    int bits = 1;
-    while ((1ull << bits) < nk) ++bits;
-    hipLaunchKernelGGL(k_seg_keys, dim3(grid_for(n, 256, 8192)), dim3(256), 0, c->stream, labels, (uint32_t)n,
-                       (uint32_t)(n / nseg), k, (const float *)nullptr, keys, payload);
-    ST_LAUNCH_CHECK();
-    radix_sort_u32(c, keys, payload, n, 0, bits, "ds.sort");
-    bounds_from_sorted(c, keys, n, (int)nk, start);
-}
-}  // namespace
 
 bool dist_assign_partials_nd(st_ctx *c, const float *const *dcols, int d, uint64_t n, int k, const float *cen,
                              uint32_t *labels, double *sums, double *sabs, int32_t *emin, uint32_t *counts) {
@@ -246,12 +255,7 @@ bool dist_assign_partials_nd(st_ctx *c, const float *const *dcols, int d, uint64
     nd_assign(c, dcols, d, n, k, cen, labels, dstate, &fz);
     if (!fz.valid) return false;  // no fused fix-up (coinciding centroids, other shapes)
     nd_fused_partials(c, d, n, k, fz, labels, sums, sabs, emin, counts);
-    c->ds_nseg = 1;
-    c->ds_k = k;
-    c->ds_d = d;
-    c->ds_n = n;
-    c->ds_labels = labels;
-    c->ds_sorted = false;  // the member order is built only if a pending pair needs it
+    set_last_partials(c, 1, k, d, n, nullptr, labels, false);  // likewise
     return true;
 }
 
@@ -260,26 +264,16 @@ void dist_partials(st_ctx *c, const float *const *cols, int d, uint64_t n, int n
     ST_REQUIRE(nseg >= 1 && n % (uint64_t)nseg == 0, ST_ERR_ARG, "kmeans partials: n must split into nseg segments");
     const uint64_t nk = (uint64_t)nseg * k;
     ST_REQUIRE(nk < (1ull << 31), ST_ERR_ARG, "kmeans partials: nseg * k too large");
-    auto *keys = wsT<uint32_t>(c, "ds.keys", n);
+    ST_REQUIRE(n < (1ull << 31), ST_ERR_ARG, "kmeans partials: n must be < 2^31 per device");
     auto *payload = wsT<uint32_t>(c, "ds.payload", n);  // value bits (1-D) or point index (N-D)
     auto *start = wsT<uint32_t>(c, "ds.start", nk + 1);
-    int bits = 1;
-    while ((1ull << bits) < nk) ++bits;
-    ST_REQUIRE(n < (1ull << 31), ST_ERR_ARG, "kmeans partials: n must be < 2^31 per device");
-    if (d == 1 && k <= 256) {
-        // stable by label inside each (contiguous) segment: one value-only counting pass per segment
+    // k <= 256 here chooses the 256-bin counting sort (seg_label_sort1d's kernels), stable by
+    // label inside each contiguous segment: the sort's own limit, not k1_accumulates' rule for
+    // the iteration, though the two bounds coincide
+    if (d == 1 && k <= 256)
         seg_label_sort1d(c, cols[0], labels, n, nseg, k, payload, start);
-    } else {
-        if (d == 1) {
-            hipLaunchKernelGGL(k_seg_keys, dim3(grid_for(n, 256, 8192)), dim3(256), 0, c->stream, labels, (uint32_t)n,
-                               (uint32_t)(n / nseg), k, cols[0], keys, payload);
-            ST_LAUNCH_CHECK();
-            radix_sort_u32(c, keys, payload, n, 0, bits, "ds.sort");
-            bounds_from_sorted(c, keys, n, (int)nk, start);
-        } else {
-            member_order_nd(c, labels, n, nseg, k);
-        }
-    }
+    else
+        member_order(c, labels, n, nseg, k, d == 1 ? cols[0] : nullptr, payload, start);
     if (d == 1) {
         partials1d(c, payload, n, start, (int)nk, sums, sabs, emin, counts);
     } else {
@@ -289,11 +283,7 @@ void dist_partials(st_ctx *c, const float *const *cols, int d, uint64_t n, int n
                            start, k, nseg, sums, sabs, emin, counts);
     }
     ST_LAUNCH_CHECK();
-    c->ds_nseg = nseg;
-    c->ds_k = k;
-    c->ds_d = d;
-    c->ds_n = n;
-    c->ds_sorted = true;
+    set_last_partials(c, nseg, k, d, n, nullptr, nullptr, true);  // the order is there: nothing to build it from
 }
 
 void dist_seqsum(st_ctx *c, int d, int k, int seg, const uint32_t *pairs, uint32_t npairs, double *running,
@@ -315,7 +305,7 @@ void dist_seqsum(st_ctx *c, int d, int k, int seg, const uint32_t *pairs, uint32
                            running);
     } else {
         if (!c->ds_sorted) {  // partials came from the fused fix-up: order the members now
-            member_order_nd(c, c->ds_labels, n, c->ds_nseg, k);
+            member_order(c, c->ds_labels, n, c->ds_nseg, k, nullptr, payload, start);
             c->ds_sorted = true;
         }
         auto *aos = wsT<float>(c, "kn.aos", n * (size_t)aos_ld(d));

@@ -54,6 +54,26 @@ __host__ __device__ inline bool sum_is_exact(double sabs, int emin) {
 // (k-means / kd-tree sort callbacks): -0 and +0 compare equal
 __host__ __device__ inline uint32_t sortkey_(float f) { return fkey_(f == 0.0f ? 0.0f : f); }
 
+// bits of a label below k (at least 1): the digits of the member sorts
+inline int label_bits(uint64_t k) {
+    int bits = 1;
+    while ((1ull << bits) < k) ++bits;
+    return bits;
+}
+
+// The path rules that more than one site applies, each stated once (the hooks are read per
+// call: tests set them around one call).
+// A 1-D update of n points and k clusters takes the accumulating assign (k_kd1_assign_acc, no
+// member sort): kmeans1d_loop and the sharded loop (kmeans_sharded, st_multi.hip).  ST_K1_SORT=1
+// sends such a call to the general iteration / the member sort.
+inline bool k1_sort_hook() { return getenv("ST_K1_SORT") != nullptr; }
+inline bool k1_accumulates(uint64_t n, int k, bool sort_hook) {
+    return k <= 256 && n > 0 && n < (1ull << 32) && !sort_hook;
+}
+// ST_ND_SORT=1: the N-D update by the member sort, not from the fused fix-up's partials
+// (kmeansnd_loop and kmeans_sharded)
+inline bool nd_sort_hook() { return getenv("ST_ND_SORT") != nullptr; }
+
 }  // namespace km
 
 // shared by the 1-D and N-D loops

@@ -653,21 +653,11 @@ __global__ __launch_bounds__(64) void k_rp_finish(const uint32_t *__restrict__ s
                                                   const int32_t *__restrict__ emin_c, const double *__restrict__ sabs_c,
                                                   const __int128 *__restrict__ total, const __int128 *__restrict__ cand_all,
                                                   float *__restrict__ cen, const double *__restrict__ base,
-                                                  double *__restrict__ sum_out, const uint32_t *__restrict__ seq_vals) {
+                                                  double *__restrict__ sum_out) {
     // one workgroup per cluster: the wave stages the candidates in LDS 256 at a time, lane 0
-    // replays them (the chain is sequential; its loads need not be).  seq_vals (non-null): the
-    // clusters left to the sequential chain (flag 2) take it here too
+    // replays them (the chain is sequential; its loads need not be)
     const int cl = blockIdx.x;
-    if (cl >= k) return;
-    const uint32_t flag0 = seq_flag[cl];
-    if (flag0 == 2u && seq_vals) {
-        if (threadIdx.x == 0) {
-            const uint32_t s0 = start[cl], s1 = start[cl + 1];
-            cen[cl] = (float)(seq_sum1d(seq_vals, s0, s1) / (double)(s1 - s0));
-        }
-        return;
-    }
-    if (flag0 != 1u) return;  // uniform per workgroup
+    if (cl >= k || seq_flag[cl] != 1u) return;  // uniform per workgroup
     __shared__ __int128 buf[256];
     const int e_lo = emin_c[cl];
     const __int128 margin = rp_margin(rp_bound(sabs_c, base, cl), e_lo);
@@ -695,11 +685,7 @@ __global__ __launch_bounds__(64) void k_rp_finish(const uint32_t *__restrict__ s
     if (threadIdx.x != 0) return;
     const __int128 fin = sv + (b0 + total[cl] - Pprev);
     if (!ok || !f64_representable(fin)) {
-        seq_flag[cl] = 2u;
-        if (seq_vals) {
-            const uint32_t s0 = start[cl], s1 = start[cl + 1];
-            cen[cl] = (float)(seq_sum1d(seq_vals, s0, s1) / (double)(s1 - s0));
-        }
+        seq_flag[cl] = 2u;  // the sequential chain takes it
         return;
     }
     if (sum_out)
@@ -717,25 +703,55 @@ uint32_t replay_cap() {
     return e ? std::min<uint32_t>((uint32_t)strtoul(e, nullptr, 10), (uint32_t)CAND_MAX) : (uint32_t)CAND_MAX;
 }
 
-// stages A-F of the chunked replay for the clusters flagged 1 (left 0 when replayed, 2 when
-// the sequential chain must take them)
-void chunked_replay(st_ctx *c, const uint32_t *vals, const uint32_t *start, int k, uint64_t maxch, const Chunk *chunks,
-                    const uint32_t *ch_first, uint32_t *seq_flag, const int32_t *emin_c, const double *sabs_c,
-                    __int128 *csum, __int128 *total, uint32_t *ccnt, uint32_t *cof, uint32_t *ctot, __int128 *cands,
-                    float *cen, const double *base, double *sum_out, bool seq_inline = false) {
-    const unsigned gch = (unsigned)std::min<uint64_t>(maxch, 2048);  // grid-stride over the chunks
-    hipLaunchKernelGGL(k_rp_sums, dim3(gch), dim3(SC_T), 0, c->stream, vals, chunks, ch_first + k, seq_flag, emin_c,
-                       csum);
-    hipLaunchKernelGGL(k_rp_prefix, dim3(k), dim3(SC_T), 0, c->stream, ch_first, k, seq_flag, sabs_c, emin_c, csum,
-                       total, base);
-    hipLaunchKernelGGL(k_rp_cands<false>, dim3(gch), dim3(SC_T), 0, c->stream, vals, chunks, ch_first + k, seq_flag,
-                       emin_c, sabs_c, csum, ccnt, cands, base);
-    hipLaunchKernelGGL(k_rp_cprefix, dim3(k), dim3(SC_T), 0, c->stream, ch_first, k, seq_flag, ccnt, cof, ctot,
+// The chunk list of k member ranges and the replay's blocks over it, each slot named here and
+// nowhere else: prefix "k1." (the loops) or "d1." (the sharded update's pieces, whose blocks a
+// loop on the same context must not share).  maxch bounds the chunks; replay = false derives
+// the chunk list alone (partials1d).
+struct ReplayWs {  // ReplayWs{c, prefix, k, maxch}
+    st_ctx *c;
+    std::string prefix;
+    int k;
+    uint64_t maxch;
+    bool replay = true;
+    uint32_t *ch_cnt = wsT<uint32_t>(c, prefix + "chcnt", (size_t)k);
+    uint32_t *ch_first = wsT<uint32_t>(c, prefix + "chfirst", (size_t)k + 1);  // [k]: the chunks' count
+    Chunk *chunks = wsT<Chunk>(c, prefix + "chunks", maxch);
+    // per chunk: exact sum, then exclusive prefix (A, B); candidates and their offsets (C, D)
+    __int128 *csum = replay ? wsT<__int128>(c, prefix + "csum", maxch) : nullptr;
+    uint32_t *ccnt = replay ? wsT<uint32_t>(c, prefix + "ccnt", maxch) : nullptr;
+    uint32_t *cof = replay ? wsT<uint32_t>(c, prefix + "cof", maxch) : nullptr;
+    // per range: candidates, exact total, the candidates' prefix sums (CAND_MAX each)
+    uint32_t *ctot = replay ? wsT<uint32_t>(c, prefix + "ctot", (size_t)k) : nullptr;
+    __int128 *total = replay ? wsT<__int128>(c, prefix + "total", (size_t)k) : nullptr;
+    __int128 *cands = replay ? wsT<__int128>(c, prefix + "cands", (size_t)k * CAND_MAX) : nullptr;
+};
+
+// what a replay writes: the centroid (cen), or from a running start (base) the f64 sum (sum_out)
+struct ReplayOut {
+    float *cen;
+    const double *base;
+    double *sum_out;
+};
+
+// stages A-F of the chunked replay for the ranges flagged 1 (left 0 when replayed, 2 when the
+// sequential chain must take them); nch bounds the chunks of this call's list
+void chunked_replay(st_ctx *c, const ReplayWs &r, uint64_t nch, const uint32_t *vals, const uint32_t *start,
+                    uint32_t *seq_flag, const int32_t *emin_c, const double *sabs_c, const ReplayOut &out) {
+    const int k = r.k;
+    const uint32_t *nchunks = r.ch_first + k;
+    const unsigned gch = (unsigned)std::min<uint64_t>(nch, 2048);  // grid-stride over the chunks
+    hipLaunchKernelGGL(k_rp_sums, dim3(gch), dim3(SC_T), 0, c->stream, vals, r.chunks, nchunks, seq_flag, emin_c,
+                       r.csum);
+    hipLaunchKernelGGL(k_rp_prefix, dim3(k), dim3(SC_T), 0, c->stream, r.ch_first, k, seq_flag, sabs_c, emin_c, r.csum,
+                       r.total, out.base);
+    hipLaunchKernelGGL(k_rp_cands<false>, dim3(gch), dim3(SC_T), 0, c->stream, vals, r.chunks, nchunks, seq_flag,
+                       emin_c, sabs_c, r.csum, r.ccnt, r.cands, out.base);
+    hipLaunchKernelGGL(k_rp_cprefix, dim3(k), dim3(SC_T), 0, c->stream, r.ch_first, k, seq_flag, r.ccnt, r.cof, r.ctot,
                        replay_cap());
-    hipLaunchKernelGGL(k_rp_cands<true>, dim3(gch), dim3(SC_T), 0, c->stream, vals, chunks, ch_first + k, seq_flag,
-                       emin_c, sabs_c, csum, cof, cands, base);
-    hipLaunchKernelGGL(k_rp_finish, dim3(k), dim3(64), 0, c->stream, start, ctot, k, seq_flag, emin_c, sabs_c, total,
-                       cands, cen, base, sum_out, seq_inline ? vals : (const uint32_t *)nullptr);
+    hipLaunchKernelGGL(k_rp_cands<true>, dim3(gch), dim3(SC_T), 0, c->stream, vals, r.chunks, nchunks, seq_flag,
+                       emin_c, sabs_c, r.csum, r.cof, r.cands, out.base);
+    hipLaunchKernelGGL(k_rp_finish, dim3(k), dim3(64), 0, c->stream, start, r.ctot, k, seq_flag, emin_c, sabs_c,
+                       r.total, r.cands, out.cen, out.base, out.sum_out);
     ST_LAUNCH_CHECK();
 }
 
@@ -801,20 +817,20 @@ __global__ __launch_bounds__(CL_T) void k_chunk_list_small(const uint32_t *__res
     }
 }
 
-// the chunk list of every cluster's member range (k clusters, start[k + 1]); acc (nullable):
-// the per-cluster accumulators to reset
-void chunk_list(st_ctx *c, const uint32_t *start, int k, uint32_t *ch_cnt, uint32_t *ch_first, Chunk *chunks,
-                SumAcc *acc = nullptr, uint32_t chsz = SC_CH) {
+// the chunk list (r.ch_first, r.chunks) of every member range of start[r.k + 1]; acc (nullable):
+// the per-range accumulators to reset
+void chunk_list(st_ctx *c, const ReplayWs &r, const uint32_t *start, SumAcc *acc = nullptr, uint32_t chsz = SC_CH) {
+    const int k = r.k;
     if (k <= CL_MAX) {
-        hipLaunchKernelGGL(k_chunk_list_small, dim3(1), dim3(CL_T), 0, c->stream, start, k, ch_first, chunks, acc,
+        hipLaunchKernelGGL(k_chunk_list_small, dim3(1), dim3(CL_T), 0, c->stream, start, k, r.ch_first, r.chunks, acc,
                            chsz);
         ST_LAUNCH_CHECK();
         return;
     }
     const unsigned gk = grid_for((uint64_t)k, 256, 1024);
-    hipLaunchKernelGGL(k_chunk_counts, dim3(gk), dim3(256), 0, c->stream, start, k, ch_cnt);
-    scan_u32(c, ch_cnt, ch_first, (uint64_t)k, ch_first + k);
-    hipLaunchKernelGGL(k_chunk_list, dim3(gk), dim3(256), 0, c->stream, start, k, ch_first, chunks);
+    hipLaunchKernelGGL(k_chunk_counts, dim3(gk), dim3(256), 0, c->stream, start, k, r.ch_cnt);
+    scan_u32(c, r.ch_cnt, r.ch_first, (uint64_t)k, r.ch_first + k);
+    hipLaunchKernelGGL(k_chunk_list, dim3(gk), dim3(256), 0, c->stream, start, k, r.ch_first, r.chunks);
     if (acc) hipLaunchKernelGGL(k_sumacc_init, dim3(gk), dim3(256), 0, c->stream, acc, k);
     ST_LAUNCH_CHECK();
 }
@@ -1853,13 +1869,6 @@ bool assign1d(st_ctx *c, const float *pts, uint64_t n, int k, const float *cen, 
 
 namespace {
 
-// bits of a label below k (at least 1): the digits of the member sorts
-int label_bits(int k) {
-    int bits = 1;
-    while ((1ull << bits) < (uint64_t)k) ++bits;
-    return bits;
-}
-
 // ST_DEBUG: the clusters whose seq_flag equals v (a read-back; waits for the stream)
 uint32_t count_flag(st_ctx *c, const uint32_t *seq_flag, int k, uint32_t v) {
     std::vector<uint32_t> f(k);
@@ -1869,142 +1878,204 @@ uint32_t count_flag(st_ctx *c, const uint32_t *seq_flag, int k, uint32_t v) {
     for (uint32_t x : f) m += x == v;
     return m;
 }
+// ST_DEBUG: one iteration's clusters without the certificate and those left to the sequential chain
+void dump_update(uint64_t n, uint32_t nflag, uint32_t nseq) {
+    fprintf(stderr, "[st k1] n=%llu uncertified=%u sequential-fallback=%u\n", (unsigned long long)n, nflag, nseq);
+}
 
-// The accumulating iteration (0 < n < 2^32, k <= 256): k_kd1_assign_acc labels the points and
-// accumulates every cluster's partials, k_kd1_final certifies the sums, scans the starts and
-// re-seeds.  Queued (the default), the k_ff_batch family then updates up to ff_max flagged
-// clusters with no read-back; more set ERR_K1_MANY and kmeans_dev reruns the call synchronised
-// (c->k1_sync).  Synchronised, the flagged count is read back each iteration and the flagged
-// clusters' members are gathered (the wave chain k_ff_count / scan / scatter up to ff_max of
-// them, the tile kernels k_flag_* past that) for the chunked replay and the sequential chain.
-void k1_accumulating(st_ctx *c, const float *pts, const float *const *dcols, uint64_t n, int k, int iters,
-                     const double *ddraws, uint64_t ndraws, State *dstate, float *cen, uint32_t *labels) {
-    auto *vals = wsT<uint32_t>(c, "k1.vals", n);
-    auto *start = wsT<uint32_t>(c, "k1.start", (size_t)k + 1);
-    auto *seq_flag = wsT<uint32_t>(c, "k1.seqflag", (size_t)k);
-    auto *emin_c = wsT<int32_t>(c, "k1.emin", (size_t)k);
-    auto *sabs_c = wsT<double>(c, "k1.sabs", (size_t)k);
-    auto *cand_buf = wsT<__int128>(c, "k1.cands", (size_t)k * CAND_MAX);
-    const uint64_t chcap = n / FL_CH + (uint64_t)k + 1;  // the flagged replay's shorter chunks
-    auto *ch_cnt = wsT<uint32_t>(c, "k1.chcnt", (size_t)k);
-    auto *ch_first = wsT<uint32_t>(c, "k1.chfirst", (size_t)k + 1);
-    auto *chunks = wsT<Chunk>(c, "k1.chunks", chcap);
-    auto *rp_csum = wsT<__int128>(c, "k1.rpcsum", chcap);
-    auto *rp_ccnt = wsT<uint32_t>(c, "k1.rpccnt", chcap);
-    auto *rp_cof = wsT<uint32_t>(c, "k1.rpcof", chcap);
-    auto *rp_ctot = wsT<uint32_t>(c, "k1.rpctot", (size_t)k);
-    auto *rp_total = wsT<__int128>(c, "k1.rptotal", (size_t)k);
-    const int kbits = label_bits(k);
-    const uint32_t ntiles = (uint32_t)((n + F1_TILE - 1) / F1_TILE);
-    auto *lab8 = wsT<uint8_t>(c, "k1.lab8", n);
-    auto *fhist = wsT<uint32_t>(c, "k1.fhist", (size_t)256 * ntiles);
-    const uint32_t G = a1_grid(ntiles);
-    auto *part = wsT<Part1>(c, "k1.part", (size_t)G * 256);
-    auto *cnt_c = wsT<uint32_t>(c, "k1.cnt", (size_t)k);
-    auto *fstart = wsT<uint32_t>(c, "k1.fstart", (size_t)k + 1);
-    auto *ticket = wsT<uint32_t>(c, "k1.ticket", 1);
-    auto *dinfo = wsT<uint32_t>(c, "k1.info", 2);
-    auto *bnd = wsT<Bnd1>(c, "k1.bnd", 256);
-    // the points' min / max keys (kmeans_dev's 1-D init)
-    const uint32_t *mm = wsT<uint32_t>(c, "km.mm", 2);
-    auto *hinfo = static_cast<uint32_t *>(pinned_slot(c, "k1.info", 8));
-    ST_HIP(hipMemsetAsync(ticket, 0, sizeof(uint32_t), c->stream));
-    // the three-pass flagged update (k_ff_batch / k_ff_bscan / k_ff_place + k_ff_finish)
-    const uint32_t nbt = (uint32_t)((n + FB_PTS - 1) / FB_PTS);
-    auto *ffz = wsT<uint32_t>(c, "k1.ffz", FF_MAX);
-    auto *ffcnt = wsT<uint32_t>(c, "k1.ffcnt", (size_t)FF_MAX * nbt);
-    auto *ffpos = wsT<uint32_t>(c, "k1.ffpos", (size_t)FF_MAX * nbt);
-    auto *fflist = wsT<uint32_t>(c, "k1.fflist", FF_MAX + 1);
-    auto *ffpool = wsT<__int128>(c, "k1.ffpool", (size_t)FF_MAX * CAND_MAX);
-    auto *ffagg = wsT<FAgg>(c, "k1.ffagg", (size_t)FF_MAX * nbt);
-    auto *fftot = wsT<FAgg>(c, "k1.fftot", FF_MAX);
-    auto *ffscr = wsT<float>(c, "k1.ffscr", (size_t)nbt * FB_PTS);
-    // queued: no read-back per iteration (more than FF_MAX flagged clusters -> ERR_K1_MANY,
-    // and kmeans_dev reruns with k1_sync); otherwise the count decides the flagged path
-    const bool queued = !c->k1_sync && !getenv("ST_K1_TILES") && !getenv("ST_K1_SYNC");
-    // flagged clusters the wave kernels take (ST_K1_FF_MAX lowers it: tests of the rerun)
-    const uint32_t ff_max = getenv("ST_K1_FF_MAX") ? std::min<uint32_t>((uint32_t)atoi(getenv("ST_K1_FF_MAX")),
-                                                                        (uint32_t)FF_MAX)
-                                                   : (uint32_t)FF_MAX;
-    for (int it = 0; it < iters; ++it) {
-        {
-            KTimer kt(c, "k1.assign");
-            hipLaunchKernelGGL(k_kd1_assign_acc<true>, dim3(G), dim3(F1_T), 0, c->stream, pts, n, cen, k,
-                               it == iters - 1 ? labels : (uint32_t *)nullptr, lab8, ntiles, part, mm, bnd);
-            ST_LAUNCH_CHECK();
-        }
-        mark(c, "k1.assign");
-        KTimer kt(c, "k1.sum");
-        hipLaunchKernelGGL(k_kd1_final, dim3(k), dim3(256), 0, c->stream, part, G, k, n, cen, seq_flag, emin_c,
-                           sabs_c, cnt_c, start, fstart, ticket, dinfo, dcols, ddraws, ndraws, dstate,
-                           queued ? ff_max : 0xffffffffu, bnd, ffz);
+// The loops' test hooks, read once per call (a test sets them around one call), each beside
+// the function that acts on it.
+struct K1Hooks {
+    bool sync;        // ST_K1_SYNC, or c->k1_sync (kmeans_dev's rerun): k1_accumulating's synchronised form
+    bool tiles;       // ST_K1_TILES: synchronised too, and gather_flagged takes the tile kernels
+    uint32_t ff_max;  // ST_K1_FF_MAX (at most FF_MAX): flagged clusters the wave kernels take
+    bool sort;        // ST_K1_SORT: kmeans1d_loop sends k <= 256 to the general iteration
+    bool debug;       // ST_DEBUG: the dump_* functions
+};
+K1Hooks k1_hooks(const st_ctx *c) {
+    const char *ff = getenv("ST_K1_FF_MAX");
+    return K1Hooks{c->k1_sync || getenv("ST_K1_SYNC"), getenv("ST_K1_TILES") != nullptr,
+                   ff ? std::min<uint32_t>((uint32_t)atoi(ff), (uint32_t)FF_MAX) : (uint32_t)FF_MAX, k1_sort_hook(),
+                   getenv("ST_DEBUG") != nullptr};
+}
+
+// one call of kmeans1d_loop: its arguments and hooks
+struct K1Call {
+    st_ctx *c;
+    const float *pts;
+    const float *const *dcols;
+    uint64_t n;
+    int k;
+    const double *ddraws;
+    uint64_t ndraws;
+    State *dstate;
+    float *cen;
+    uint32_t *labels;
+    K1Hooks h;
+};
+
+// what the accumulating assign, k_kd1_final and the flagged updates share
+struct AccWs {  // AccWs{c, n, k}
+    st_ctx *c;
+    uint64_t n;
+    int k;
+    uint32_t ntiles = (uint32_t)((n + F1_TILE - 1) / F1_TILE);
+    uint32_t G = a1_grid(ntiles);                                     // the assign's workgroups
+    Part1 *part = wsT<Part1>(c, "k1.part", (size_t)G * 256);          // one partial per workgroup and cluster
+    uint8_t *lab8 = wsT<uint8_t>(c, "k1.lab8", n);                    // every iteration's labels
+    uint32_t *fhist = wsT<uint32_t>(c, "k1.fhist", (size_t)256 * ntiles);  // the synchronised gathers' counts
+    uint32_t *cnt = wsT<uint32_t>(c, "k1.cnt", (size_t)k);
+    uint32_t *start = wsT<uint32_t>(c, "k1.start", (size_t)k + 1);    // the clusters' starts (re-seeding)
+    uint32_t *fstart = wsT<uint32_t>(c, "k1.fstart", (size_t)k + 1);  // the flagged clusters' member ranges
+    uint32_t *ticket = wsT<uint32_t>(c, "k1.ticket", 1);              // k_kd1_final's last workgroup
+    uint32_t *info = wsT<uint32_t>(c, "k1.info", 2);                  // flagged clusters, their members
+    uint32_t *hinfo = static_cast<uint32_t *>(pinned_slot(c, "k1.info", 8));  // read back (synchronised)
+    Bnd1 *bnd = wsT<Bnd1>(c, "k1.bnd", 256);
+    uint32_t *seq_flag = wsT<uint32_t>(c, "k1.seqflag", (size_t)k);   // 1: replay, 2: sequential chain
+    int32_t *emin = wsT<int32_t>(c, "k1.emin", (size_t)k);
+    double *sabs = wsT<double>(c, "k1.sabs", (size_t)k);
+    uint32_t *vals = wsT<uint32_t>(c, "k1.vals", n);                  // the flagged clusters' members, in point order
+    const uint32_t *mm = wsT<uint32_t>(c, "km.mm", 2);                // the points' min / max keys (kmeans_dev's init)
+};
+
+// the three-pass flagged update (k_ff_batch / k_ff_bscan / k_ff_place + k_ff_finish)
+struct FfWs {  // FfWs{c, n}
+    st_ctx *c;
+    uint64_t n;
+    uint32_t nbt = (uint32_t)((n + FB_PTS - 1) / FB_PTS);  // batches
+    uint32_t *ffz = wsT<uint32_t>(c, "k1.ffz", FF_MAX);
+    uint32_t *ffcnt = wsT<uint32_t>(c, "k1.ffcnt", (size_t)FF_MAX * nbt);
+    uint32_t *ffpos = wsT<uint32_t>(c, "k1.ffpos", (size_t)FF_MAX * nbt);
+    uint32_t *fflist = wsT<uint32_t>(c, "k1.fflist", FF_MAX + 1);
+    __int128 *ffpool = wsT<__int128>(c, "k1.ffpool", (size_t)FF_MAX * CAND_MAX);
+    FAgg *ffagg = wsT<FAgg>(c, "k1.ffagg", (size_t)FF_MAX * nbt);
+    FAgg *fftot = wsT<FAgg>(c, "k1.fftot", FF_MAX);
+    float *ffscr = wsT<float>(c, "k1.ffscr", (size_t)nbt * FB_PTS);
+};
+
+// ---- the accumulating iteration's phases, in the order they run -------------------------
+// k_kd1_assign_acc labels the points (labels: the last iteration's, else null) and accumulates
+// every cluster's partials
+void acc_assign(const K1Call &q, const AccWs &a, uint32_t *labels) {
+    st_ctx *c = q.c;
+    {
+        KTimer kt(c, "k1.assign");
+        hipLaunchKernelGGL(k_kd1_assign_acc<true>, dim3(a.G), dim3(F1_T), 0, c->stream, q.pts, q.n, q.cen, q.k, labels,
+                           a.lab8, a.ntiles, a.part, a.mm, a.bnd);
         ST_LAUNCH_CHECK();
+    }
+    mark(c, "k1.assign");
+}
+
+// k_kd1_final certifies the sums, scans the starts, re-seeds and counts the flagged clusters:
+// more than ff_limit of them set ERR_K1_MANY
+void acc_final(const K1Call &q, const AccWs &a, const FfWs &f, uint32_t ff_limit) {
+    hipLaunchKernelGGL(k_kd1_final, dim3(q.k), dim3(256), 0, q.c->stream, a.part, a.G, q.k, q.n, q.cen, a.seq_flag,
+                       a.emin, a.sabs, a.cnt, a.start, a.fstart, a.ticket, a.info, q.dcols, q.ddraws, q.ndraws,
+                       q.dstate, ff_limit, a.bnd, f.ffz);
+    ST_LAUNCH_CHECK();
+}
+
+// The queued flagged update, behind the final with no read-back: its kernels find the flagged
+// clusters on the device and return at once when there are none.
+void flagged_queued(const K1Call &q, const AccWs &a, const FfWs &f, __int128 *cands) {
+    st_ctx *c = q.c;
+    const uint32_t nbt = f.nbt;
+    const unsigned gb = (unsigned)std::min<uint64_t>((nbt + 3) / 4, 2048);
+    hipLaunchKernelGGL(k_ff_batch, dim3(gb), dim3(256), 0, c->stream, a.lab8, q.pts, q.n, nbt, q.k, a.seq_flag, a.emin,
+                       a.sabs, f.ffscr, f.ffagg, f.fflist);
+    hipLaunchKernelGGL(k_ff_bscan, dim3(FF_MAX), dim3(FN_T), 0, c->stream, nbt, f.fflist, f.ffagg, f.fftot);
+    const unsigned gp = (unsigned)std::min<uint64_t>(((uint64_t)FF_MAX * nbt + 3) / 4, 4096);
+    hipLaunchKernelGGL(k_ff_place, dim3(gp), dim3(256), 0, c->stream, nbt, f.fflist, a.fstart, a.emin, a.sabs, f.ffscr,
+                       f.ffagg, f.ffz, a.vals, f.ffpool, f.ffcnt, f.ffpos, f.fftot);
+    hipLaunchKernelGGL(k_ff_finish, dim3(FF_MAX), dim3(FN_T), 0, c->stream, nbt, f.fflist, a.seq_flag, a.fstart, a.emin,
+                       a.sabs, f.fftot, a.vals, f.ffpool, f.ffcnt, f.ffpos, cands, replay_cap(), q.cen, q.dstate);
+    ST_LAUNCH_CHECK();
+}
+
+// ST_DEBUG after a queued update: the flagged clusters, their members and replay candidates
+// (a read-back; waits for the stream)
+void dump_queued(const K1Call &q, const AccWs &a, const FfWs &f) {
+    st_ctx *c = q.c;
+    const int k = q.k;
+    uint32_t hfl[FF_MAX + 1], hz[FF_MAX];
+    std::vector<uint32_t> f2(k), fs(k + 1);
+    ST_HIP(hipMemcpyAsync(hfl, f.fflist, sizeof hfl, hipMemcpyDeviceToHost, c->stream));
+    ST_HIP(hipMemcpyAsync(hz, f.ffz, sizeof hz, hipMemcpyDeviceToHost, c->stream));
+    ST_HIP(hipMemcpyAsync(f2.data(), a.seq_flag, 4 * k, hipMemcpyDeviceToHost, c->stream));
+    ST_HIP(hipMemcpyAsync(fs.data(), a.fstart, 4 * (k + 1), hipMemcpyDeviceToHost, c->stream));
+    ST_HIP(hipStreamSynchronize(c->stream));
+    fprintf(stderr, "[st k1] n=%llu flagged=%u", (unsigned long long)q.n, hfl[0]);
+    for (uint32_t i = 0; i < hfl[0] && i < (uint32_t)FF_MAX; ++i)
+        fprintf(stderr, " c%u:members=%u,cands=%u,seq=%u", hfl[1 + i], fs[hfl[1 + i] + 1] - fs[hfl[1 + i]], hz[i],
+                f2[hfl[1 + i]] == 2u ? 1u : 0u);
+    fprintf(stderr, "\n");
+}
+
+// the nflag flagged clusters' members in point order (a.vals, ranges a.fstart): the wave chain
+// up to ff_max clusters, the tile kernels past that or under ST_K1_TILES
+void gather_flagged(const K1Call &q, const AccWs &a, uint32_t nflag) {
+    st_ctx *c = q.c;
+    const uint64_t n = q.n;
+    const int k = q.k;
+    if (nflag <= q.h.ff_max && !q.h.tiles) {
+        const uint32_t nch = (uint32_t)((n + FF_CH - 1) / FF_CH);
+        hipLaunchKernelGGL(k_ff_count, dim3(a.G), dim3(256), 0, c->stream, a.lab8, n, nch, k, a.seq_flag, a.fhist);
+        hipLaunchKernelGGL(k_ff_scan, dim3(nflag), dim3(FS_T), 0, c->stream, a.fhist, nch, k, a.seq_flag, a.fstart);
+        hipLaunchKernelGGL(k_ff_scatter, dim3(a.G), dim3(256), 0, c->stream, a.lab8, q.pts, n, nch, k, a.seq_flag,
+                           a.fhist, a.vals);
+    } else {
+        hipLaunchKernelGGL(k_flag_tiles, dim3(a.G), dim3(F1_T), 0, c->stream, a.lab8, n, a.ntiles, k, a.seq_flag,
+                           a.fhist);
+        hipLaunchKernelGGL(k_flag_scan, dim3(k), dim3(SC_T), 0, c->stream, a.fhist, a.ntiles, a.seq_flag, a.fstart);
+        hipLaunchKernelGGL(k_flag_scatter, dim3(a.G), dim3(F1_T), 0, c->stream, a.lab8, q.pts, n, a.ntiles, k,
+                           label_bits(k), a.seq_flag, a.fhist, a.vals);
+    }
+    ST_LAUNCH_CHECK();
+}
+
+// The synchronised flagged update: the flagged count is read back, the flagged clusters'
+// members are gathered, replayed over short chunks (the flagged clusters are few, so their
+// replay passes run over many workgroups at once) and, where the replay gives up, summed by
+// the sequential chain.
+void flagged_synchronised(const K1Call &q, const AccWs &a, const ReplayWs &r) {
+    st_ctx *c = q.c;
+    ST_HIP(hipMemcpyAsync(a.hinfo, a.info, 8, hipMemcpyDeviceToHost, c->stream));
+    ST_HIP(hipStreamSynchronize(c->stream));
+    const uint32_t nflag = a.hinfo[0], ftotal = a.hinfo[1];
+    uint32_t nseq = 0;
+    if (nflag) {
+        gather_flagged(q, a, nflag);
+        chunk_list(c, r, a.fstart, nullptr, FL_CH);
+        chunked_replay(c, r, ftotal / FL_CH + nflag + 1, a.vals, a.fstart, a.seq_flag, a.emin, a.sabs,
+                       ReplayOut{q.cen, nullptr, nullptr});
+        if (q.h.debug) nseq = count_flag(c, a.seq_flag, q.k, 2u);
+        hipLaunchKernelGGL(k_sum1d_seq, dim3(q.k), dim3(64), 0, c->stream, a.vals, a.fstart, a.seq_flag, q.cen);
+        ST_LAUNCH_CHECK();
+    }
+    if (q.h.debug) dump_update(q.n, nflag, nseq);
+}
+
+// The accumulating iteration (0 < n < 2^32, k <= 256).  Queued (the default), up to ff_max
+// flagged clusters are updated with no read-back; more set ERR_K1_MANY and kmeans_dev reruns
+// the call synchronised (c->k1_sync).
+void k1_accumulating(const K1Call &q, int iters) {
+    st_ctx *c = q.c;
+    const AccWs a{c, q.n, q.k};
+    const FfWs f{c, q.n};
+    const ReplayWs r{c, "k1.", q.k, q.n / FL_CH + (uint64_t)q.k + 1};  // the flagged replay's shorter chunks
+    ST_HIP(hipMemsetAsync(a.ticket, 0, sizeof(uint32_t), c->stream));
+    const bool queued = !q.h.sync && !q.h.tiles;
+    for (int it = 0; it < iters; ++it) {
+        acc_assign(q, a, it == iters - 1 ? q.labels : (uint32_t *)nullptr);
+        KTimer kt(c, "k1.sum");  // to the end of the update, as the row has always been
+        acc_final(q, a, f, queued ? q.h.ff_max : 0xffffffffu);
         if (queued) {
-            // the flagged path queued behind the final with no read-back: its kernels find
-            // the flagged clusters on the device and return at once when there are none
-            const unsigned gb = (unsigned)std::min<uint64_t>((nbt + 3) / 4, 2048);
-            hipLaunchKernelGGL(k_ff_batch, dim3(gb), dim3(256), 0, c->stream, lab8, pts, n, nbt, k, seq_flag,
-                               emin_c, sabs_c, ffscr, ffagg, fflist);
-            hipLaunchKernelGGL(k_ff_bscan, dim3(FF_MAX), dim3(FN_T), 0, c->stream, nbt, fflist, ffagg, fftot);
-            const unsigned gp = (unsigned)std::min<uint64_t>(((uint64_t)FF_MAX * nbt + 3) / 4, 4096);
-            hipLaunchKernelGGL(k_ff_place, dim3(gp), dim3(256), 0, c->stream, nbt, fflist, fstart, emin_c,
-                               sabs_c, ffscr, ffagg, ffz, vals, ffpool, ffcnt, ffpos, fftot);
-            hipLaunchKernelGGL(k_ff_finish, dim3(FF_MAX), dim3(FN_T), 0, c->stream, nbt, fflist, seq_flag,
-                               fstart, emin_c, sabs_c, fftot, vals, ffpool, ffcnt, ffpos, cand_buf,
-                               replay_cap(), cen, dstate);
-            ST_LAUNCH_CHECK();
-            if (getenv("ST_DEBUG")) {  // flagged clusters, their members and replay candidates
-                uint32_t hfl[FF_MAX + 1], hz[FF_MAX];
-                std::vector<uint32_t> f2(k), fs(k + 1);
-                ST_HIP(hipMemcpyAsync(hfl, fflist, sizeof hfl, hipMemcpyDeviceToHost, c->stream));
-                ST_HIP(hipMemcpyAsync(hz, ffz, sizeof hz, hipMemcpyDeviceToHost, c->stream));
-                ST_HIP(hipMemcpyAsync(f2.data(), seq_flag, 4 * k, hipMemcpyDeviceToHost, c->stream));
-                ST_HIP(hipMemcpyAsync(fs.data(), fstart, 4 * (k + 1), hipMemcpyDeviceToHost, c->stream));
-                ST_HIP(hipStreamSynchronize(c->stream));
-                fprintf(stderr, "[st k1] n=%llu flagged=%u", (unsigned long long)n, hfl[0]);
-                for (uint32_t f = 0; f < hfl[0] && f < (uint32_t)FF_MAX; ++f)
-                    fprintf(stderr, " c%u:members=%u,cands=%u,seq=%u", hfl[1 + f],
-                            fs[hfl[1 + f] + 1] - fs[hfl[1 + f]], hz[f], f2[hfl[1 + f]] == 2u ? 1u : 0u);
-                fprintf(stderr, "\n");
-            }
-            mark(c, "k1.update");
-            continue;
+            flagged_queued(q, a, f, r.cands);
+            if (q.h.debug) dump_queued(q, a, f);
+        } else {
+            flagged_synchronised(q, a, r);
         }
-        ST_HIP(hipMemcpyAsync(hinfo, dinfo, 8, hipMemcpyDeviceToHost, c->stream));
-        ST_HIP(hipStreamSynchronize(c->stream));
-        const uint32_t nflag = hinfo[0], ftotal = hinfo[1];
-        uint32_t nseq = 0;
-        if (nflag) {
-            // the flagged clusters' members in point order (fvals, starts fstart), then
-            // the chunked replay and, where it gives up, the sequential chain
-            if (nflag <= ff_max && !getenv("ST_K1_TILES")) {
-                const uint32_t nch = (uint32_t)((n + FF_CH - 1) / FF_CH);
-                hipLaunchKernelGGL(k_ff_count, dim3(G), dim3(256), 0, c->stream, lab8, n, nch, k, seq_flag, fhist);
-                hipLaunchKernelGGL(k_ff_scan, dim3(nflag), dim3(FS_T), 0, c->stream, fhist, nch, k, seq_flag,
-                                   fstart);
-                hipLaunchKernelGGL(k_ff_scatter, dim3(G), dim3(256), 0, c->stream, lab8, pts, n, nch, k, seq_flag,
-                                   fhist, vals);
-            } else {
-                hipLaunchKernelGGL(k_flag_tiles, dim3(G), dim3(F1_T), 0, c->stream, lab8, n, ntiles, k, seq_flag,
-                                   fhist);
-                hipLaunchKernelGGL(k_flag_scan, dim3(k), dim3(SC_T), 0, c->stream, fhist, ntiles, seq_flag, fstart);
-                hipLaunchKernelGGL(k_flag_scatter, dim3(G), dim3(F1_T), 0, c->stream, lab8, pts, n, ntiles, k,
-                                   kbits, seq_flag, fhist, vals);
-            }
-            ST_LAUNCH_CHECK();
-            // short chunks: the flagged clusters are few, their replay passes run over many
-            // workgroups at once
-            const uint64_t fch = ftotal / FL_CH + nflag + 1;
-            chunk_list(c, fstart, k, ch_cnt, ch_first, chunks, nullptr, FL_CH);
-            chunked_replay(c, vals, fstart, k, fch, chunks, ch_first, seq_flag, emin_c, sabs_c, rp_csum, rp_total,
-                           rp_ccnt, rp_cof, rp_ctot, cand_buf, cen, nullptr, nullptr);
-            if (getenv("ST_DEBUG")) nseq = count_flag(c, seq_flag, k, 2u);
-            hipLaunchKernelGGL(k_sum1d_seq, dim3(k), dim3(64), 0, c->stream, vals, fstart, seq_flag, cen);
-            ST_LAUNCH_CHECK();
-        }
-        if (getenv("ST_DEBUG"))
-            fprintf(stderr, "[st k1] n=%llu uncertified=%u sequential-fallback=%u\n", (unsigned long long)n, nflag,
-                    nseq);
         mark(c, "k1.update");
     }
 }
@@ -2013,70 +2084,60 @@ void k1_accumulating(st_ctx *c, const float *pts, const float *const *dcols, uin
 // k <= KD1_LDS), a stable radix sort by label, every cluster's sums over SC_CH-member chunks,
 // the chunked replay and the sequential chain for the sums that fail the certificate, then
 // the empty clusters' re-seeding.
-void k1_general(st_ctx *c, const float *pts, const float *const *dcols, uint64_t n, int k, int iters,
-                const double *ddraws, uint64_t ndraws, State *dstate, float *cen, uint32_t *labels) {
+void k1_general(const K1Call &q, int iters) {
+    st_ctx *c = q.c;
+    const uint64_t n = q.n;
+    const int k = q.k;
     auto *keys = wsT<uint32_t>(c, "k1.keys", n);
     auto *vals = wsT<uint32_t>(c, "k1.vals", n);
     auto *start = wsT<uint32_t>(c, "k1.start", (size_t)k + 1);
     auto *seq_flag = wsT<uint32_t>(c, "k1.seqflag", (size_t)k);
     auto *emin_c = wsT<int32_t>(c, "k1.emin", (size_t)k);
     auto *sabs_c = wsT<double>(c, "k1.sabs", (size_t)k);
-    auto *cand_buf = wsT<__int128>(c, "k1.cands", (size_t)k * CAND_MAX);
-    const uint64_t maxch = n / SC_CH + (uint64_t)k + 1;
-    auto *ch_cnt = wsT<uint32_t>(c, "k1.chcnt", (size_t)k);
-    auto *ch_first = wsT<uint32_t>(c, "k1.chfirst", (size_t)k + 1);
-    auto *chunks = wsT<Chunk>(c, "k1.chunks", maxch);
     auto *acc = wsT<SumAcc>(c, "k1.acc", (size_t)k);
-    auto *rp_csum = wsT<__int128>(c, "k1.rpcsum", maxch);
-    auto *rp_ccnt = wsT<uint32_t>(c, "k1.rpccnt", maxch);
-    auto *rp_cof = wsT<uint32_t>(c, "k1.rpcof", maxch);
-    auto *rp_ctot = wsT<uint32_t>(c, "k1.rpctot", (size_t)k);
-    auto *rp_total = wsT<__int128>(c, "k1.rptotal", (size_t)k);
-    const int kbits = label_bits(k);
-    const bool debug = getenv("ST_DEBUG") != nullptr;
+    const ReplayWs r{c, "k1.", k, n / SC_CH + (uint64_t)k + 1};
     for (int it = 0; it < iters; ++it) {
-        const bool paired = assign1d(c, pts, n, k, cen, labels, keys, vals, it == iters - 1);
+        const bool paired = assign1d(c, q.pts, n, k, q.cen, q.labels, keys, vals, it == iters - 1);
         mark(c, "k1.assign");
         if (!paired) {
-            hipLaunchKernelGGL(k_pairs1d, dim3(grid_for(n, 256, 8192)), dim3(256), 0, c->stream, pts, labels, n, keys,
-                               vals);
+            hipLaunchKernelGGL(k_pairs1d, dim3(grid_for(n, 256, 8192)), dim3(256), 0, c->stream, q.pts, q.labels, n,
+                               keys, vals);
             ST_LAUNCH_CHECK();
         }
         uint32_t *skeys = keys, *svals = vals;  // where the sort leaves its result (no copy back)
-        radix_sort_u32_inplace_or_swap(c, keys, vals, n, 0, kbits, "k1.msort", &skeys, &svals);
+        radix_sort_u32_inplace_or_swap(c, keys, vals, n, 0, label_bits(k), "k1.msort", &skeys, &svals);
         bounds_from_sorted(c, skeys, n, k, start);
         {
             KTimer kt(c, "k1.sum");
-            chunk_list(c, start, k, ch_cnt, ch_first, chunks, acc);
-            hipLaunchKernelGGL(k_sum1d_chunks, dim3(maxch), dim3(SC_T), 0, c->stream, svals, chunks, ch_first + k, acc);
+            chunk_list(c, r, start, acc);
+            hipLaunchKernelGGL(k_sum1d_chunks, dim3(r.maxch), dim3(SC_T), 0, c->stream, svals, r.chunks, r.ch_first + k,
+                               acc);
             hipLaunchKernelGGL(k_sum1d_final, dim3(grid_for((uint64_t)k, 256, 1024)), dim3(256), 0, c->stream, acc,
-                               start, k, cen, seq_flag, emin_c, sabs_c);
+                               start, k, q.cen, seq_flag, emin_c, sabs_c);
             ST_LAUNCH_CHECK();
-            const uint32_t nflag = debug ? count_flag(c, seq_flag, k, 1u) : 0u;
-            chunked_replay(c, svals, start, k, maxch, chunks, ch_first, seq_flag, emin_c, sabs_c, rp_csum, rp_total,
-                           rp_ccnt, rp_cof, rp_ctot, cand_buf, cen, nullptr, nullptr);
-            if (debug)
-                fprintf(stderr, "[st k1] n=%llu uncertified=%u sequential-fallback=%u\n", (unsigned long long)n, nflag,
-                        count_flag(c, seq_flag, k, 2u));
-            hipLaunchKernelGGL(k_sum1d_seq, dim3(k), dim3(64), 0, c->stream, svals, start, seq_flag, cen);
+            const uint32_t nflag = q.h.debug ? count_flag(c, seq_flag, k, 1u) : 0u;
+            chunked_replay(c, r, r.maxch, svals, start, seq_flag, emin_c, sabs_c, ReplayOut{q.cen, nullptr, nullptr});
+            if (q.h.debug) dump_update(n, nflag, count_flag(c, seq_flag, k, 2u));
+            hipLaunchKernelGGL(k_sum1d_seq, dim3(k), dim3(64), 0, c->stream, svals, start, seq_flag, q.cen);
             ST_LAUNCH_CHECK();
         }
-        reseed_empty(c, dcols, 1, n, k, start, ddraws, ndraws, dstate, cen);
+        reseed_empty(c, q.dcols, 1, n, k, start, q.ddraws, q.ndraws, q.dstate, q.cen);
         mark(c, "k1.update");
     }
 }
 
 }  // namespace
 
-// The two iterations and the inputs that take them: k <= 256, cluster1d's codebooks, the
-// accumulating one; everything else the general one.  ST_K1_SORT=1 (test hook) sends k <= 256
-// to the general iteration too.
+// The two iterations and the inputs that take them (k1_accumulates, st_kmeans.h): k <= 256,
+// cluster1d's codebooks, the accumulating one; everything else the general one.  ST_K1_SORT=1
+// (test hook) sends k <= 256 to the general iteration too.
 void kmeans1d_loop(st_ctx *c, const float *pts, const float *const *dcols, uint64_t n, int k, int iters,
                    const double *ddraws, uint64_t ndraws, State *dstate, float *cen, uint32_t *labels) {
-    if (k <= 256 && n > 0 && n < (1ull << 32) && !getenv("ST_K1_SORT"))
-        k1_accumulating(c, pts, dcols, n, k, iters, ddraws, ndraws, dstate, cen, labels);
+    const K1Call q{c, pts, dcols, n, k, ddraws, ndraws, dstate, cen, labels, k1_hooks(c)};
+    if (k1_accumulates(n, k, q.h.sort))
+        k1_accumulating(q, iters);
     else
-        k1_general(c, pts, dcols, n, k, iters, ddraws, ndraws, dstate, cen, labels);
+        k1_general(q, iters);
 }
 
 // the sharded 1-D member order: a stable sort by (segment, label) is a stable sort by label inside
@@ -2132,40 +2193,27 @@ void assign_partials1d(st_ctx *c, const float *pts, uint64_t n, int nseg, int k,
 
 void partials1d(st_ctx *c, const uint32_t *vals, uint64_t n, const uint32_t *start, int nk, double *sums, double *sabs,
                 int32_t *emin, uint32_t *counts) {
-    const uint64_t maxch = n / SC_CH + (uint64_t)nk + 1;
-    auto *ch_cnt = wsT<uint32_t>(c, "d1.chcnt", (size_t)nk);
-    auto *ch_first = wsT<uint32_t>(c, "d1.chfirst", (size_t)nk + 1);
-    auto *chunks = wsT<Chunk>(c, "d1.chunks", maxch);
+    const ReplayWs r{c, "d1.", nk, n / SC_CH + (uint64_t)nk + 1, false};  // the chunk list alone
     auto *acc = wsT<SumAcc>(c, "d1.acc", (size_t)nk);
-    chunk_list(c, start, nk, ch_cnt, ch_first, chunks, acc);
+    chunk_list(c, r, start, acc);
     const unsigned gk = grid_for((uint64_t)nk, 256, 1024);
-    hipLaunchKernelGGL(k_sum1d_chunks, dim3(maxch), dim3(SC_T), 0, c->stream, vals, chunks, ch_first + nk, acc);
+    hipLaunchKernelGGL(k_sum1d_chunks, dim3(r.maxch), dim3(SC_T), 0, c->stream, vals, r.chunks, r.ch_first + nk, acc);
     hipLaunchKernelGGL(k_partials_out, dim3(gk), dim3(256), 0, c->stream, acc, start, nk, sums, sabs, emin, counts);
     ST_LAUNCH_CHECK();
 }
 
 void seqsum1d(st_ctx *c, const uint32_t *vals, uint64_t n, const uint32_t *start, int k, const uint32_t *pairs,
               uint32_t npairs, double *running, const int32_t *emin, const double *sabs, uint32_t *pflag) {
-    const uint64_t maxch = n / SC_CH + (uint64_t)k + 1;
-    auto *ch_cnt = wsT<uint32_t>(c, "d1.chcnt", (size_t)k);
-    auto *ch_first = wsT<uint32_t>(c, "d1.chfirst", (size_t)k + 1);
-    auto *chunks = wsT<Chunk>(c, "d1.chunks", maxch);
+    const ReplayWs r{c, "d1.", k, n / SC_CH + (uint64_t)k + 1};
     auto *flag_cl = wsT<uint32_t>(c, "d1.flag", (size_t)k);
     auto *base_cl = wsT<double>(c, "d1.base", (size_t)k);
     auto *sum_cl = wsT<double>(c, "d1.sum", (size_t)k);
-    auto *csum = wsT<__int128>(c, "d1.csum", maxch);
-    auto *ccnt = wsT<uint32_t>(c, "d1.ccnt", maxch);
-    auto *cof = wsT<uint32_t>(c, "d1.cof", maxch);
-    auto *ctot = wsT<uint32_t>(c, "d1.ctot", (size_t)k);
-    auto *total = wsT<__int128>(c, "d1.total", (size_t)k);
-    auto *cands = wsT<__int128>(c, "d1.cands", (size_t)k * CAND_MAX);
     ST_HIP(hipMemsetAsync(flag_cl, 0, sizeof(uint32_t) * k, c->stream));
     const unsigned gp = grid_for(npairs, 256, 1024);
     hipLaunchKernelGGL(k_pend_in, dim3(gp), dim3(256), 0, c->stream, pairs, npairs, running, flag_cl, base_cl);
     ST_LAUNCH_CHECK();
-    chunk_list(c, start, k, ch_cnt, ch_first, chunks);
-    chunked_replay(c, vals, start, k, maxch, chunks, ch_first, flag_cl, emin, sabs, csum, total, ccnt, cof, ctot, cands,
-                   nullptr, base_cl, sum_cl);
+    chunk_list(c, r, start);
+    chunked_replay(c, r, r.maxch, vals, start, flag_cl, emin, sabs, ReplayOut{nullptr, base_cl, sum_cl});
     hipLaunchKernelGGL(k_pend_out, dim3(gp), dim3(256), 0, c->stream, pairs, npairs, flag_cl, sum_cl, running, pflag);
     ST_LAUNCH_CHECK();
     if (getenv("ST_DEBUG")) {

@@ -2800,7 +2800,7 @@ void kmeansnd_loop(st_ctx *c, const float *const *dcols, int d, uint64_t n, int 
         if (c->verify && it == iters - 1)
             ST_HIP(hipMemcpyAsync(ws(c, "verify.prev", cbytes), cen, cbytes, hipMemcpyDeviceToDevice, c->stream));
         NdFused fz;
-        fz.want = !aos64 && !getenv("ST_ND_SORT");
+        fz.want = !aos64 && !km::nd_sort_hook();
         nd_assign(c, dcols, d, n, k, cen, labels, dstate, &fz, pending ? settle : std::function<bool()>());
         // update
         if (fz.valid) {

@@ -519,9 +519,9 @@ uint64_t kmeans_sharded(st_ctx *c, Coll &co, const Points &P, int k, int iters, 
         bool folded = false;  // the partials are already in sac / E
         if (c->verify && d > 1 && it == iters - 1)  // st_ctx_set_verify: the last assign's centroids
             ST_HIP(hipMemcpyAsync(ws(c, "verify.prev", cbytes), cen, cbytes, hipMemcpyDeviceToDevice, c->stream));
-        if (P.n && d == 1 && k <= 256 && !getenv("ST_K1_SORT")) {
+        if (d == 1 && km::k1_accumulates(P.n, k, km::k1_sort_hook())) {
             dist_assign_partials1d(c, P.pts[0], P.n, P.nseg, k, cen, labels, sums, sabs, emin, counts);
-        } else if (P.n && d > 1 && P.nseg == 1 && !getenv("ST_ND_SORT")) {
+        } else if (P.n && d > 1 && P.nseg == 1 && !km::nd_sort_hook()) {
             // the fused fix-up's partials (ST_ND_SORT=1: the member sort), written straight into
             // the all-reduce's layout (one segment: nothing to fold but the counts)
             folded = dist_assign_partials_nd(c, dpts, d, P.n, k, cen, labels, sac, sac + dk, E, counts);
