@@ -304,9 +304,12 @@ int st_dev_sog(st_ctx *ctx, const st_table *table, int32_t iters, const double *
  * *out_m = m, *out_sh_coeffs = C.  st_dev_compressed_ply: the same over device columns
  * (transformed in place, like the reference's table) into device outputs. */
 enum st_action_kind {
-    ST_ACTION_TRANSFORM = 1, ST_ACTION_FILTER_NAN, ST_ACTION_FILTER_VALUE, ST_ACTION_FILTER_BANDS, ST_ACTION_PARAM
+    ST_ACTION_TRANSFORM = 1, ST_ACTION_FILTER_NAN, ST_ACTION_FILTER_VALUE, ST_ACTION_FILTER_BANDS, ST_ACTION_PARAM,
+    /* this project's own kinds: "importance, decimation and crops" below */
+    ST_ACTION_ORDER_IMPORTANCE, ST_ACTION_DECIMATE, ST_ACTION_FILTER_BOX, ST_ACTION_FILTER_SPHERE
 };
 enum st_compare { ST_CMP_LT = 0, ST_CMP_LTE, ST_CMP_GT, ST_CMP_GTE, ST_CMP_EQ, ST_CMP_NEQ };
+enum st_decimate_mode { ST_DECIMATE_COUNT = 0, ST_DECIMATE_FRACTION = 1 };
 typedef struct {
     int32_t kind;                    /* st_action_kind */
     int32_t compare;                 /* ST_ACTION_FILTER_VALUE: st_compare */
@@ -314,6 +317,12 @@ typedef struct {
     double value;                    /* ST_ACTION_FILTER_VALUE */
     int32_t bands;                   /* ST_ACTION_FILTER_BANDS: output bands 0..3 */
     st_transform_params transform;   /* ST_ACTION_TRANSFORM */
+    /* appended for the kinds after ST_ACTION_PARAM; a zero-filled st_action stays valid for the old ones */
+    double box_min[3], box_max[3];   /* ST_ACTION_FILTER_BOX: the corners */
+    double center[3];                /* ST_ACTION_FILTER_SPHERE */
+    double radius;                   /* ST_ACTION_FILTER_SPHERE */
+    double amount;                   /* ST_ACTION_DECIMATE: the row count or the fraction */
+    int32_t amount_mode;             /* ST_ACTION_DECIMATE: st_decimate_mode */
 } st_action;
 int st_process(st_ctx *ctx, const st_ttable *src, const st_action *actions, int32_t nactions, const st_ttable *dst,
                uint64_t *out_m);
@@ -1214,6 +1223,59 @@ int st_dev_summary(st_ctx *ctx, const st_ttable *dev_table, st_col_summary *out)
 int st_summary(st_ctx *ctx, const st_ttable *host_table, st_col_summary *out);
 int st_summary_text(const st_ttable *t, const st_col_summary *s, char **out, uint64_t *size);
 const char *st_ctx_last_summary_stats(st_ctx *ctx);
+
+/* ---- importance, decimation and crops -----------------------------------------------------------
+ * Making a scene smaller on purpose: the rows that matter most, the rows inside a box or a sphere,
+ * the rows in the order a progressive viewer should draw them.  The reference at this version has
+ * none of these, so the rules are this project's own.  csrc/st_importance.h holds every rule as a
+ * host/device function and a serial host form of the three selections.
+ *
+ * Every value is the column's element as a JS number (any st_ply_type, widened exactly); all
+ * arithmetic is IEEE double, each operation rounds once in the order written, nothing is fused.
+ *   score      s = (scale_0 + scale_1) + scale_2; score = exp(s) * sigmoid(opacity), exp and sigmoid
+ *              those of csrc/st_jsmath.h (V8's).  The convention of the original .splat converter.
+ *              A score is in [+0, +Infinity] or NaN: Infinity * 0 is NaN, and a NaN in any of the four
+ *              values gives NaN.  A table without one of the four columns is ST_ERR_ARG (for
+ *              ST_ACTION_ORDER_IMPORTANCE and ST_ACTION_DECIMATE too); nothing is launched.
+ *   key        NaN ? 0 : bits(score) + 1 as uint64: larger is more important, every NaN is 0.
+ *   importance order   descending key; equal keys (NaN among NaN included) by ascending row index: a
+ *              total order that depends only on the data.  rank(i) = row i's position in it.
+ *   ST_ACTION_ORDER_IMPORTANCE (orderByImportance)   permuteRows by that order; n <= 1 does nothing.
+ *   ST_ACTION_DECIMATE (decimate)   keeps the m rows of rank < m in their original row order (a
+ *              stable selection, like the filters).  amount_mode ST_DECIMATE_COUNT: amount must be a
+ *              finite, non-negative, integer-valued double below 2^53 (else ST_ERR_ARG), m =
+ *              min(amount, n).  ST_DECIMATE_FRACTION: 0 <= amount <= 1 (else ST_ERR_ARG, NaN included),
+ *              m = min(n, floor(amount * (double)n)), the product in f64.  Another mode is ST_ERR_ARG.
+ *              m == n keeps the table as it is (permuteRows by the identity); m == 0 leaves no row.
+ *   ST_ACTION_FILTER_BOX (filterBox)   keep iff x >= box_min[0] && x <= box_max[0] && y >= box_min[1]
+ *              && y <= box_max[1] && z >= box_min[2] && z <= box_max[2]: faces inclusive, any NaN
+ *              (coordinate or bound) false, infinite bounds open a side (Infinity <= Infinity holds),
+ *              min > max keeps nothing.  A missing x, y or z column reads as NaN: every row is dropped,
+ *              as for filterByValue's missing column.
+ *   ST_ACTION_FILTER_SPHERE (filterSphere)   dx = x - center[0], dy, dz alike; keep iff
+ *              ((dx*dx + dy*dy) + dz*dz) < radius*radius.  Strict: radius 0 keeps nothing; a negative
+ *              radius behaves as its square does; a NaN anywhere keeps nothing; missing columns as
+ *              for the box.
+ * All four copy the table the way a filter does.  In st_group_sog_bundle_process the box and the
+ * sphere are row-local and run in the per-rank slices; ST_ACTION_DECIMATE and
+ * ST_ACTION_ORDER_IMPORTANCE are global and are refused there with ST_ERR_UNSUPPORTED before any rank
+ * uploads.  (The st_set_devices group of the one-call forms runs the actions on one device before
+ * the rows are sharded: every kind works.)
+ *
+ * The stand-alone calls take a device table of n < 2^32 rows (ST_ERR_UNSUPPORTED above), columns
+ * aligned to their types, work on the context stream and wait for it:
+ *   st_dev_importance        dev_scores[i] = row i's score (n doubles)
+ *   st_dev_importance_order  dev_order[j] = the row of rank j (n uint32)
+ *   st_dev_importance_top    the rows of rank < min(m, n), ascending, into dev_rows (capacity
+ *                            min(m, n) uint32); *out_m = their count.  The key of rank m - 1 is found
+ *                            by a radix select over the keys (8-bit digits from the top, LDS block
+ *                            histograms merged with integer atomics, digits picked on the device,
+ *                            the rounds queued without a host round trip); rows above it are kept,
+ *                            rows equal to it in row order until m are.  All integer: the result
+ *                            does not depend on the launch shape. */
+int st_dev_importance(st_ctx *ctx, const st_ttable *dev_table, double *dev_scores);
+int st_dev_importance_order(st_ctx *ctx, const st_ttable *dev_table, uint32_t *dev_order);
+int st_dev_importance_top(st_ctx *ctx, const st_ttable *dev_table, uint64_t m, uint32_t *dev_rows, uint64_t *out_m);
 
 /* ---- st_dev_probe: a test hook ----------------------------------------------------------------
  * The two layers under every bit-exact result, called directly so that tests can compare them

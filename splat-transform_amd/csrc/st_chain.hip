@@ -95,6 +95,14 @@ struct Chain {
 
 void run_actions(Chain &ch, const st_action *actions, int nactions) {
     const int in_coeffs = ch.coeffs();  // filterBands reads the ORIGINAL table (process.ts:111)
+    // the importance kinds' argument errors before anything is launched (no action adds or removes
+    // a scale or opacity column, and the amount's validity does not depend on the row count)
+    for (int a = 0; a < nactions; ++a) {
+        if (actions[a].kind != ST_ACTION_DECIMATE && actions[a].kind != ST_ACTION_ORDER_IMPORTANCE) continue;
+        const bool dec = actions[a].kind == ST_ACTION_DECIMATE;
+        importance_require(ch.typed(), dec ? "decimate" : "orderByImportance");
+        if (dec) (void)decimate_rows_checked(actions[a], 0);
+    }
     for (int a = 0; a < nactions; ++a) {
         const st_action &act = actions[a];
         switch (act.kind) {
@@ -134,6 +142,33 @@ void run_actions(Chain &ch, const st_action *actions, int nactions) {
             }
             case ST_ACTION_PARAM:
                 break;
+            // this project's own kinds (st_abi.h, "importance, decimation and crops"): row
+            // selections and one reordering, all through permuteRows like the filters
+            case ST_ACTION_FILTER_BOX:
+            case ST_ACTION_FILTER_SPHERE: {
+                if (ch.n == 0) break;
+                auto *idx = wsT<uint32_t>(ch.c, ch.tag + ".idx", ch.n);
+                const uint64_t m = act.kind == ST_ACTION_FILTER_BOX
+                                       ? filter_box_tdev(ch.c, ch.typed(), act.box_min, act.box_max, ch.tag, idx)
+                                       : filter_sphere_tdev(ch.c, ch.typed(), act.center, act.radius, ch.tag, idx);
+                if (m != ch.n) ch.gather(idx, m);
+                break;
+            }
+            case ST_ACTION_DECIMATE: {
+                const uint64_t m = decimate_rows_checked(act, ch.n);
+                if (m == ch.n) break;  // every row kept: permuteRows by the identity
+                auto *idx = wsT<uint32_t>(ch.c, ch.tag + ".idx", ch.n);
+                if (m) importance_top_tdev(ch.c, ch.typed(), m, ch.tag, idx);
+                ch.gather(idx, m);
+                break;
+            }
+            case ST_ACTION_ORDER_IMPORTANCE: {
+                if (ch.n <= 1) break;
+                auto *idx = wsT<uint32_t>(ch.c, ch.tag + ".idx", ch.n);
+                importance_order_tdev(ch.c, ch.typed(), ch.tag, idx);
+                ch.gather(idx, ch.n);
+                break;
+            }
             default:
                 throw Error(ST_ERR_ARG, "process: unknown action kind " + std::to_string(act.kind));
         }

@@ -330,6 +330,18 @@ uint64_t compact_flags_dev(st_ctx *c, const uint32_t *flags, uint64_t n, uint32_
 uint64_t filter_value_tdev(st_ctx *c, const st_ttable *t, const char *column, int32_t cmp, double value,
                            uint32_t *out_idx);
 void permute_rows_tdev(st_ctx *c, const st_ttable *src, const uint32_t *idx, uint64_t m, const st_ttable *dst);
+// importance, decimation and crops (st_importance.hip; the rules: st_importance.h).  Workspace slots
+// go under `tag`.  importance_require: ST_ERR_ARG unless t has scale_0..2 and opacity (no launch).
+// importance_top_tdev wants 0 < m < n.  The crops and the top return the kept rows' count (sync)
+void importance_require(const st_ttable *t, const char *what);
+void importance_scores_tdev(st_ctx *c, const st_ttable *t, double *scores);
+void importance_order_tdev(st_ctx *c, const st_ttable *t, const std::string &tag, uint32_t *out_idx);
+uint64_t importance_top_tdev(st_ctx *c, const st_ttable *t, uint64_t m, const std::string &tag, uint32_t *out_idx);
+uint64_t filter_box_tdev(st_ctx *c, const st_ttable *t, const double lo[3], const double hi[3], const std::string &tag,
+                         uint32_t *out_idx);
+uint64_t filter_sphere_tdev(st_ctx *c, const st_ttable *t, const double centre[3], double radius,
+                            const std::string &tag, uint32_t *out_idx);
+uint64_t decimate_rows_checked(const st_action &act, uint64_t n);  // decimate's m, or ST_ERR_ARG
 int combine_layout(const st_ttable *const *srcs, int nsrc, int32_t *col_table, int32_t *col_index);
 void combine_tdev(st_ctx *c, const st_ttable *const *srcs, int nsrc, const st_ttable *dst);
 void morton_order_dev(st_ctx *c, const float *x, const float *y, const float *z, uint32_t *indices, uint64_t n);

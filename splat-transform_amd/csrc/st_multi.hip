@@ -1275,6 +1275,12 @@ static uint64_t group_sog(st_group *g, const st_table *const *tabs, int ntab, co
         ST_REQUIRE(splits[0] == 0 && splits[world] == N, ST_ERR_ARG, "group: splits must run from 0 to the row count");
         for (int r = 0; r < world; ++r) ST_REQUIRE(splits[r] <= splits[r + 1], ST_ERR_ARG, "group: splits must ascend");
     }
+    // decimate and orderByImportance rank rows against the whole input: a rank's slice cannot (the
+    // box and the sphere are row-local and run below).  Refused before any rank uploads
+    for (int t = 0; t < ntab && actions; ++t)
+        for (int a = 0; a < nactions[t]; ++a)
+            ST_REQUIRE(actions[t][a].kind != ST_ACTION_DECIMATE && actions[t][a].kind != ST_ACTION_ORDER_IMPORTANCE,
+                       ST_ERR_UNSUPPORTED, "group: decimate / orderByImportance need the whole table on one device");
     std::vector<uint64_t> used(world, 0);
     g->run([&](int r) {
         st_ctx *c = g->ctx[r];

@@ -250,7 +250,12 @@ const packCompressed = (dataTable) => {
 // ProcessAction objects as the reference's CLI builds them (process.ts:6-42): Vec3 values for
 // translate / rotate, a number for scale, {columnName, comparator, value} for filterByValue.
 // Normalised for the addon: k = st_action_kind, transform params as t / r / s.
-const ACTION = { transform: 1, filterNaN: 2, filterByValue: 3, filterBands: 4, param: 5 };
+// This project's own kinds (st_abi.h, "importance, decimation and crops"): filterBox {min, max},
+// filterSphere {center, radius}, decimate {count} or {fraction}, orderByImportance; a point is a Vec3
+// or an array of three numbers.
+const ACTION = { transform: 1, filterNaN: 2, filterByValue: 3, filterBands: 4, param: 5,
+    orderByImportance: 6, decimate: 7, filterBox: 8, filterSphere: 9 };
+const vec3 = v => (Array.isArray(v) ? [Number(v[0]), Number(v[1]), Number(v[2])] : [Number(v.x), Number(v.y), Number(v.z)]);
 const COMPARE = { lt: 0, lte: 1, gt: 2, gte: 3, eq: 4, neq: 5 };
 const normaliseActions = actions => actions.map((a) => {
     switch (a.kind) {
@@ -272,6 +277,16 @@ const normaliseActions = actions => actions.map((a) => {
             return { k: ACTION.filterBands, bands: a.value };
         case 'param':
             return { k: ACTION.param };
+        case 'filterBox':
+            return { k: ACTION.filterBox, min: vec3(a.min), max: vec3(a.max) };
+        case 'filterSphere':
+            return { k: ACTION.filterSphere, center: vec3(a.center), radius: Number(a.radius) };
+        case 'decimate':  // mode 0: count, 1: fraction (st_decimate_mode)
+            return a.fraction === undefined ?
+                { k: ACTION.decimate, mode: 0, amount: Number(a.count) } :
+                { k: ACTION.decimate, mode: 1, amount: Number(a.fraction) };
+        case 'orderByImportance':
+            return { k: ACTION.orderByImportance };
         default:
             return { k: 0 };  // unknown kinds: the reference's switch ignores them
     }
@@ -303,7 +318,8 @@ const processSchema = (dataTable, actions) => {
 // renames, its columns keep the input's arrays): those run first and are written back into the
 // input arrays, the rest runs on the mutated table.
 const isTransform = a => a.kind === 'translate' || a.kind === 'rotate' || a.kind === 'scale';
-const isFilter = a => a.kind === 'filterNaN' || a.kind === 'filterByValue';
+const isFilter = a => a.kind === 'filterNaN' || a.kind === 'filterByValue' || a.kind === 'filterBox' ||
+    a.kind === 'filterSphere' || a.kind === 'decimate' || a.kind === 'orderByImportance';
 const processDataTable = (dataTable, processActions) => {
     const cols = () => dataTable.columns.map(c => c.data);
     const names = dataTable.columns.map(c => c.name);

@@ -55,6 +55,7 @@
  */
 #define _GNU_SOURCE /* clock_gettime, madvise */
 #include <node_api.h>
+#include <math.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -556,6 +557,16 @@ static double prop_num(napi_env env, napi_value obj, const char *k) {
     return num(env, v);
 }
 
+/* obj[k] as three numbers (a missing property or element reads NaN: the comparison then fails) */
+static void prop_vec3(napi_env env, napi_value obj, const char *k, double out[3]) {
+    napi_value v, e;
+    for (uint32_t j = 0; j < 3; ++j) {
+        out[j] = NAN;
+        if (napi_get_named_property(env, obj, k, &v) == napi_ok && napi_get_element(env, v, j, &e) == napi_ok)
+            napi_get_value_double(env, e, &out[j]);
+    }
+}
+
 static int parse_actions(napi_env env, napi_value actions, chain_args *a);
 
 static int chain_parse(napi_env env, napi_value cols, napi_value names, napi_value actions, chain_args *a) {
@@ -604,6 +615,18 @@ static int parse_actions(napi_env env, napi_value actions, chain_args *a) {
         if (x->kind == ST_ACTION_FILTER_VALUE && napi_get_named_property(env, o, "column", &v) == napi_ok) {
             if (!(a->acols[i] = dup_str(env, v, "splat-hip: filterByValue needs a column name string"))) return 0;
             x->column = a->acols[i];
+        }
+        if (x->kind == ST_ACTION_FILTER_BOX) {
+            prop_vec3(env, o, "min", x->box_min);
+            prop_vec3(env, o, "max", x->box_max);
+        }
+        if (x->kind == ST_ACTION_FILTER_SPHERE) {
+            prop_vec3(env, o, "center", x->center);
+            x->radius = prop_num(env, o, "radius");
+        }
+        if (x->kind == ST_ACTION_DECIMATE) {
+            x->amount_mode = (int32_t)prop_num(env, o, "mode");
+            x->amount = prop_num(env, o, "amount");
         }
         if (x->kind == ST_ACTION_TRANSFORM) {
             double t[3], r[4];

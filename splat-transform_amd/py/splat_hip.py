@@ -62,10 +62,14 @@ class SogTextures(ctypes.Structure):
 
 class Action(ctypes.Structure):
     _fields_ = [('kind', ctypes.c_int32), ('compare', ctypes.c_int32), ('column', ctypes.c_char_p),
-                ('value', ctypes.c_double), ('bands', ctypes.c_int32), ('transform', TransformParams)]
+                ('value', ctypes.c_double), ('bands', ctypes.c_int32), ('transform', TransformParams),
+                ('box_min', ctypes.c_double * 3), ('box_max', ctypes.c_double * 3), ('center', ctypes.c_double * 3),
+                ('radius', ctypes.c_double), ('amount', ctypes.c_double), ('amount_mode', ctypes.c_int32)]
 
 
 ACTION_TRANSFORM, ACTION_FILTER_NAN, ACTION_FILTER_VALUE, ACTION_FILTER_BANDS, ACTION_PARAM = 1, 2, 3, 4, 5
+ACTION_ORDER_IMPORTANCE, ACTION_DECIMATE, ACTION_FILTER_BOX, ACTION_FILTER_SPHERE = 6, 7, 8, 9
+DECIMATE_COUNT, DECIMATE_FRACTION = 0, 1
 COMPARE = {'lt': 0, 'lte': 1, 'gt': 2, 'gte': 3, 'eq': 4, 'neq': 5}
 
 
@@ -142,6 +146,7 @@ EXPORTS = [
     'st_gzip_member_layout', 'st_inflate_head', 'st_dev_inflate', 'st_dev_gunzip', 'st_spz_gz_layout', 'st_spz_gz_read',
     'st_dev_spz_gz_read',
     'st_dev_summary', 'st_summary', 'st_summary_text', 'st_ctx_last_summary_stats',
+    'st_dev_importance', 'st_dev_importance_order', 'st_dev_importance_top',
     'st_dev_probe',
 ]
 
@@ -238,6 +243,14 @@ def ply_type_of(a):
                 torch.float32: 7, torch.float64: 8}
         return tmap[a.dtype]
     return _NP_TO_PLY[np.dtype(a.dtype)]
+
+
+def _torch_type(dtype):
+    import torch
+    return {np.dtype(n): t for n, t in (
+        (np.int8, torch.int8), (np.uint8, torch.uint8), (np.int16, torch.int16), (np.uint16, torch.uint16),
+        (np.int32, torch.int32), (np.uint32, torch.uint32), (np.float32, torch.float32),
+        (np.float64, torch.float64))}[np.dtype(dtype)]
 
 
 def make_ttable(cols, n=None):
@@ -449,7 +462,9 @@ def action_params(kind, value):
 def make_actions(actions):
     """processDataTable's ProcessAction list (process.ts:6-42) as st_action[]: dicts with 'kind' in
     translate / rotate / scale (value as in action_params), filterNaN, filterByValue (columnName,
-    comparator, value), filterBands (value), param"""
+    comparator, value), filterBands (value), param; and this project's own (st_abi.h, "importance,
+    decimation and crops"): filterBox (min, max: three numbers each), filterSphere (center, radius),
+    decimate (count or fraction), orderByImportance"""
     arr = (Action * max(1, len(actions)))()
     keep = []
     for a, act in zip(arr, actions):
@@ -467,6 +482,18 @@ def make_actions(actions):
             a.kind, a.bands = ACTION_FILTER_BANDS, int(act['value'])
         elif k == 'param':
             a.kind = ACTION_PARAM
+        elif k == 'filterBox':
+            a.kind, a.box_min, a.box_max = ACTION_FILTER_BOX, _vec3(act['min']), _vec3(act['max'])
+        elif k == 'filterSphere':
+            a.kind, a.center, a.radius = ACTION_FILTER_SPHERE, _vec3(act['center']), float(act['radius'])
+        elif k == 'decimate':
+            if ('count' in act) == ('fraction' in act):
+                raise ValueError('decimate takes either count or fraction')
+            a.kind = ACTION_DECIMATE
+            a.amount_mode = DECIMATE_COUNT if 'count' in act else DECIMATE_FRACTION
+            a.amount = float(act['count'] if 'count' in act else act['fraction'])
+        elif k == 'orderByImportance':
+            a.kind = ACTION_ORDER_IMPORTANCE
         else:
             raise ValueError(k)
     arr._keep = keep
@@ -496,7 +523,8 @@ def process_schema(items, actions, with_source=False):
 
 
 TRANSFORM_KINDS = ('translate', 'rotate', 'scale')
-FILTER_KINDS = ('filterNaN', 'filterByValue')
+# the kinds that copy the table (the four after filterByValue are this project's own)
+FILTER_KINDS = ('filterNaN', 'filterByValue', 'filterBox', 'filterSphere', 'decimate', 'orderByImportance')
 
 
 def sog_geometry(n, sh_coeffs):
@@ -1029,6 +1057,7 @@ class Context:
             except RuntimeError:
                 pass  # no device: st_ctx_create reports it
         self.h = ctypes.c_void_p()
+        self.device = device
         self.last_inflate = None        # 'host' or 'device': the way the last read_spz / read_spz_dev went
         self.last_inflate_stats = None  # st_inflate_stats of the last device inflate, as far as it got
         check(lib().st_ctx_create(ctypes.c_int32(device), ctypes.byref(self.h)))
@@ -1118,6 +1147,54 @@ class Context:
     def summary(self, cols):
         """st_summary: the same of host columns (numpy arrays), uploaded through the staged copies"""
         return self._summary(lib().st_summary, cols)
+
+    def dev_importance(self, cols):
+        """st_dev_importance: exp((scale_0 + scale_1) + scale_2) * sigmoid(opacity) of every row of
+        device columns (list of (name, tensor) or a dict, any of the eight types) -> float64 tensor"""
+        import torch
+        t = make_ttable(cols)
+        out = torch.empty(t.n, dtype=torch.float64, device=f'cuda:{self.device}')
+        check(lib().st_dev_importance(self.h, ctypes.byref(t), _ptr(out)))
+        return out
+
+    def dev_importance_order(self, cols):
+        """st_dev_importance_order: the rows from the most important down (descending score, NaN
+        last, ties by row index) -> torch.int32 tensor holding the uint32 row indices"""
+        import torch
+        t = make_ttable(cols)
+        out = torch.empty(t.n, dtype=torch.int32, device=f'cuda:{self.device}')
+        check(lib().st_dev_importance_order(self.h, ctypes.byref(t), _ptr(out)))
+        return out
+
+    def dev_importance_top(self, cols, m):
+        """st_dev_importance_top: the min(m, n) most important rows' indices, ascending (decimate's
+        selection) -> torch.int32 tensor holding the uint32 row indices"""
+        import torch
+        t = make_ttable(cols)
+        k = min(int(m), t.n)
+        out = torch.empty(k, dtype=torch.int32, device=f'cuda:{self.device}')
+        got = ctypes.c_uint64()
+        check(lib().st_dev_importance_top(self.h, ctypes.byref(t), ctypes.c_uint64(int(m)), _ptr(out), ctypes.byref(got)))
+        assert got.value == k
+        return out
+
+    def _upload(self, cols):
+        import torch
+        items = list(cols.items()) if isinstance(cols, dict) else list(cols)
+        out = []
+        for k, a in items:  # as bytes: every one of the eight types, whatever torch converts
+            a = np.ascontiguousarray(a)
+            raw = torch.from_numpy(a.view(np.uint8).reshape(-1)).to(f'cuda:{self.device}')
+            out.append((k, raw.view(_torch_type(a.dtype))))
+        return out
+
+    def importance(self, cols):
+        """the scores of host columns (numpy arrays), uploaded -> float64 array"""
+        return self.dev_importance(self._upload(cols)).cpu().numpy()
+
+    def importance_order(self, cols):
+        """the importance order of host columns (numpy arrays), uploaded -> uint32 array"""
+        return self.dev_importance_order(self._upload(cols)).cpu().numpy().view(np.uint32)
 
     def summary_stats(self):
         """the last summary's sum paths (st_ctx_last_summary_stats) as a dict: columns, fast, general,
