@@ -306,10 +306,13 @@ int st_dev_sog(st_ctx *ctx, const st_table *table, int32_t iters, const double *
 enum st_action_kind {
     ST_ACTION_TRANSFORM = 1, ST_ACTION_FILTER_NAN, ST_ACTION_FILTER_VALUE, ST_ACTION_FILTER_BANDS, ST_ACTION_PARAM,
     /* this project's own kinds: "importance, decimation and crops" below */
-    ST_ACTION_ORDER_IMPORTANCE, ST_ACTION_DECIMATE, ST_ACTION_FILTER_BOX, ST_ACTION_FILTER_SPHERE
+    ST_ACTION_ORDER_IMPORTANCE, ST_ACTION_DECIMATE, ST_ACTION_FILTER_BOX, ST_ACTION_FILTER_SPHERE,
+    /* "neighbour distances and outliers" below */
+    ST_ACTION_FILTER_OUTLIERS
 };
 enum st_compare { ST_CMP_LT = 0, ST_CMP_LTE, ST_CMP_GT, ST_CMP_GTE, ST_CMP_EQ, ST_CMP_NEQ };
 enum st_decimate_mode { ST_DECIMATE_COUNT = 0, ST_DECIMATE_FRACTION = 1 };
+enum st_outlier_mode { ST_OUTLIER_SIGMA = 0, ST_OUTLIER_DISTANCE = 1 };
 typedef struct {
     int32_t kind;                    /* st_action_kind */
     int32_t compare;                 /* ST_ACTION_FILTER_VALUE: st_compare */
@@ -323,6 +326,9 @@ typedef struct {
     double radius;                   /* ST_ACTION_FILTER_SPHERE */
     double amount;                   /* ST_ACTION_DECIMATE: the row count or the fraction */
     int32_t amount_mode;             /* ST_ACTION_DECIMATE: st_decimate_mode */
+    int32_t neighbors;               /* ST_ACTION_FILTER_OUTLIERS: k, 1..32 */
+    int32_t outlier_mode;            /* ST_ACTION_FILTER_OUTLIERS: st_outlier_mode */
+    double outlier_value;            /* ST_ACTION_FILTER_OUTLIERS: sigma, or the distance */
 } st_action;
 int st_process(st_ctx *ctx, const st_ttable *src, const st_action *actions, int32_t nactions, const st_ttable *dst,
                uint64_t *out_m);
@@ -1276,6 +1282,53 @@ const char *st_ctx_last_summary_stats(st_ctx *ctx);
 int st_dev_importance(st_ctx *ctx, const st_ttable *dev_table, double *dev_scores);
 int st_dev_importance_order(st_ctx *ctx, const st_ttable *dev_table, uint32_t *dev_order);
 int st_dev_importance_top(st_ctx *ctx, const st_ttable *dev_table, uint64_t m, uint32_t *dev_rows, uint64_t *out_m);
+
+/* ---- neighbour distances and outliers ---------------------------------------------------------------
+ * Cleaning a scene: trained Gaussian scenes carry "floaters", isolated rows far from any surface, that
+ * stretch the extents every writer quantises over.  The reference at this version has no such
+ * command, so the rules are this project's own, in the style of the two sections above: a result
+ * depends only on the data -- not on the order of the rows, the shape of a launch or the search
+ * structure -- and is checked bit for bit.  csrc/st_neighbors.h holds every rule as a host/device
+ * function and a plain serial host form.
+ *
+ * Every value is the column's element as a JS number (any st_ply_type, widened exactly); all
+ * arithmetic is IEEE double, each operation rounds once in the order written, nothing is fused.
+ *   placed     row i is placed iff its x, y and z are all finite.  A table without an x, y or z column
+ *              is ST_ERR_ARG (the message names the column); nothing is launched.
+ *   d2(i, j)   for placed i != j: dx = x_i - x_j, dy, dz alike; d2 = (dx*dx + dy*dy) + dz*dz.  It may
+ *              be +Infinity and is never NaN.  Rows that coincide are still distinct rows: only j = i
+ *              is excluded.
+ *   dist_k(i)  i not placed: NaN, the one quiet NaN 0x7ff8000000000000.  Fewer than k other rows
+ *              placed: +Infinity.  Otherwise sqrt of the k-th smallest element, with multiplicity, of
+ *              the multiset { d2(i, j) : j placed, j != i }.  A property of a multiset: no tie rule
+ *              is needed, and any correct search gives the same bits.
+ *   k          an integer in 1..32; anything else is ST_ERR_ARG before any launch.
+ *   ST_ACTION_FILTER_OUTLIERS (filterOutliers)   neighbors = k; keep iff dist_k(i) <= t.
+ *              outlier_mode ST_OUTLIER_SIGMA: t = mean + outlier_value * std_dev, one multiplication
+ *              and one addition, mean and std_dev those of the column summary over the finite dist_k
+ *              values of the table as it is at that point of the chain; outlier_value may be any
+ *              double but NaN (ST_ERR_ARG).  ST_OUTLIER_DISTANCE: t = outlier_value; NaN is
+ *              ST_ERR_ARG.  Another mode is ST_ERR_ARG.  Rows that are not placed go; rows with a
+ *              dist_k of +Infinity go unless t is +Infinity; with no finite dist_k the sigma mode has
+ *              t = NaN and keeps nothing.  A stable selection through permuteRows, like the filters;
+ *              all rows kept: the table stays as it is; n = 0 does nothing.
+ * The action is global: st_group_sog_bundle_process refuses it with ST_ERR_UNSUPPORTED before any
+ * rank uploads, as it does ST_ACTION_DECIMATE.  (The st_set_devices group of the one-call forms runs
+ * the actions on one device first: it works there.)
+ *
+ * st_dev_neighbor_dist: dev_dist[i] = dist_k(i) for a device table of n < 2^32 rows
+ * (ST_ERR_UNSUPPORTED above), columns aligned to their types; it works on the context stream and
+ * waits for it.  The search: the placed rows sorted by a 30-bit Morton key of their own (locality
+ * only: no result depends on it), leaves of L consecutive sorted rows with exact boxes, an implicit
+ * 8-ary tree of boxes above them; one wave takes a leaf as its queries and prunes a node when, for
+ * every one of them, a lower bound of d2 -- computed with d2's own operations in d2's order, so that
+ * IEEE rounding's monotonicity makes it a bound on the COMPUTED d2 and no tolerance exists anywhere --
+ * is >= that query's k-th best so far.  ST_KNN_LEAF=<4..64>, read per call, sets L (default 64; an invalid value falls
+ * back to it).
+ * st_ctx_last_neighbor_stats: the last call's JSON -- {"rows", "placed", "leaves", "levels" (box
+ * levels, leaves to root), "pairs" (d2 evaluations), "nodes" (box tests)}. */
+int st_dev_neighbor_dist(st_ctx *ctx, const st_ttable *dev_table, int32_t k, double *dev_dist);
+const char *st_ctx_last_neighbor_stats(st_ctx *ctx);
 
 /* ---- st_dev_probe: a test hook ----------------------------------------------------------------
  * The two layers under every bit-exact result, called directly so that tests can compare them

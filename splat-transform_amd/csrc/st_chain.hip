@@ -97,7 +97,9 @@ void run_actions(Chain &ch, const st_action *actions, int nactions) {
     const int in_coeffs = ch.coeffs();  // filterBands reads the ORIGINAL table (process.ts:111)
     // the importance kinds' argument errors before anything is launched (no action adds or removes
     // a scale or opacity column, and the amount's validity does not depend on the row count)
+    // (filterOutliers alike: no action adds or removes a position column)
     for (int a = 0; a < nactions; ++a) {
+        if (actions[a].kind == ST_ACTION_FILTER_OUTLIERS) outliers_require(ch.typed(), actions[a]);
         if (actions[a].kind != ST_ACTION_DECIMATE && actions[a].kind != ST_ACTION_ORDER_IMPORTANCE) continue;
         const bool dec = actions[a].kind == ST_ACTION_DECIMATE;
         importance_require(ch.typed(), dec ? "decimate" : "orderByImportance");
@@ -167,6 +169,15 @@ void run_actions(Chain &ch, const st_action *actions, int nactions) {
                 auto *idx = wsT<uint32_t>(ch.c, ch.tag + ".idx", ch.n);
                 importance_order_tdev(ch.c, ch.typed(), ch.tag, idx);
                 ch.gather(idx, ch.n);
+                break;
+            }
+            // st_abi.h, "neighbour distances and outliers": dist_k into a slot under the chain's tag,
+            // the threshold from the summary's device steps on that column, a stable selection
+            case ST_ACTION_FILTER_OUTLIERS: {
+                if (ch.n == 0) break;
+                auto *idx = wsT<uint32_t>(ch.c, ch.tag + ".idx", ch.n);
+                const uint64_t m = filter_outliers_tdev(ch.c, ch.typed(), act, ch.tag, idx);
+                if (m != ch.n) ch.gather(idx, m);
                 break;
             }
             default:

@@ -154,6 +154,8 @@ struct st_ctx {
     std::string last_kn_stats = "{}";
     // the last column summary's sum paths (st_ctx_last_summary_stats)
     std::string last_summary_stats = "{}";
+    // the last neighbour search's sizes and work (st_ctx_last_neighbor_stats)
+    std::string last_neighbor_stats = "{}";
     // kernel profiling (st_ctx_set_profiling)
     bool profiling = false;
     struct KEv {
@@ -342,6 +344,16 @@ uint64_t filter_box_tdev(st_ctx *c, const st_ttable *t, const double lo[3], cons
 uint64_t filter_sphere_tdev(st_ctx *c, const st_ttable *t, const double centre[3], double radius,
                             const std::string &tag, uint32_t *out_idx);
 uint64_t decimate_rows_checked(const st_action &act, uint64_t n);  // decimate's m, or ST_ERR_ARG
+// neighbour distances and outliers (st_neighbors.hip; the rules: st_neighbors.h).  Workspace slots go
+// under `tag`.  neighbors_require: ST_ERR_ARG unless t has x, y and z and k is in 1..32 (no launch);
+// outliers_require: that, and the action's mode and value.  neighbor_dist_tdev queues dist_k of every
+// row into dist (n doubles) and waits once on the way (the placed count).  filter_outliers_tdev:
+// the kept rows ascending into out_idx, their count returned (sync)
+void neighbors_require(const st_ttable *t, int32_t k, const char *what);
+void outliers_require(const st_ttable *t, const st_action &act);
+void neighbor_dist_tdev(st_ctx *c, const st_ttable *t, int32_t k, const std::string &tag, double *dist);
+uint64_t filter_outliers_tdev(st_ctx *c, const st_ttable *t, const st_action &act, const std::string &tag,
+                              uint32_t *out_idx);
 int combine_layout(const st_ttable *const *srcs, int nsrc, int32_t *col_table, int32_t *col_index);
 void combine_tdev(st_ctx *c, const st_ttable *const *srcs, int nsrc, const st_ttable *dst);
 void morton_order_dev(st_ctx *c, const float *x, const float *y, const float *z, uint32_t *indices, uint64_t n);
@@ -517,6 +529,9 @@ bool gunzip_dev(st_ctx *c, const uint8_t *dev_in, uint64_t n, uint8_t *dev_out, 
 // wait for the stream and leave the sum paths taken in c->last_summary_stats
 void summary_dev(st_ctx *c, const st_ttable *t, st_col_summary *out);
 void summary_host(st_ctx *c, const st_ttable *t, st_col_summary *out);
+// the same device steps on one float64 column, for a caller inside the library (filterOutliers'
+// threshold): waits for the stream, leaves st_ctx_last_summary_stats as it was
+void summary_f64_dev(st_ctx *c, const double *col, uint64_t n, st_col_summary *out);
 
 // the .ksplat writer (st_ksplat_write.hip; the rules: st_abi.h, "the .ksplat writer").  ksplat_params
 // checks mode, degree (-1: the table's own), block size and harmonics range against a table picked

@@ -1278,9 +1278,13 @@ static uint64_t group_sog(st_group *g, const st_table *const *tabs, int ntab, co
     // decimate and orderByImportance rank rows against the whole input: a rank's slice cannot (the
     // box and the sphere are row-local and run below).  Refused before any rank uploads
     for (int t = 0; t < ntab && actions; ++t)
-        for (int a = 0; a < nactions[t]; ++a)
+        for (int a = 0; a < nactions[t]; ++a) {
             ST_REQUIRE(actions[t][a].kind != ST_ACTION_DECIMATE && actions[t][a].kind != ST_ACTION_ORDER_IMPORTANCE,
                        ST_ERR_UNSUPPORTED, "group: decimate / orderByImportance need the whole table on one device");
+            // a row's neighbours may lie in another rank's slice
+            ST_REQUIRE(actions[t][a].kind != ST_ACTION_FILTER_OUTLIERS, ST_ERR_UNSUPPORTED,
+                       "group: filterOutliers needs the whole table on one device");
+        }
     std::vector<uint64_t> used(world, 0);
     g->run([&](int r) {
         st_ctx *c = g->ctx[r];

@@ -472,6 +472,13 @@ void summary_dev(st_ctx *c, const st_ttable *t, st_col_summary *out) {
     publish(c, P);
 }
 
+void summary_f64_dev(st_ctx *c, const double *col, uint64_t n, st_col_summary *out) {
+    ST_REQUIRE(((uintptr_t)col & 7u) == 0, ST_ERR_INTERNAL, "summary_f64_dev: misaligned column");
+    Paths P;
+    read_switches(P);
+    summarize_batch(c, {SmCol{col, ST_PLY_DOUBLE, 0}}, n, out, P);
+}
+
 void summary_host(st_ctx *c, const st_ttable *t, st_col_summary *out) {
     check_table(t);
     Paths P;

@@ -252,9 +252,10 @@ const packCompressed = (dataTable) => {
 // Normalised for the addon: k = st_action_kind, transform params as t / r / s.
 // This project's own kinds (st_abi.h, "importance, decimation and crops"): filterBox {min, max},
 // filterSphere {center, radius}, decimate {count} or {fraction}, orderByImportance; a point is a Vec3
-// or an array of three numbers.
+// or an array of three numbers.  And ("neighbour distances and outliers") filterOutliers {k, sigma} or
+// {k, distance}; k defaults to 8.
 const ACTION = { transform: 1, filterNaN: 2, filterByValue: 3, filterBands: 4, param: 5,
-    orderByImportance: 6, decimate: 7, filterBox: 8, filterSphere: 9 };
+    orderByImportance: 6, decimate: 7, filterBox: 8, filterSphere: 9, filterOutliers: 10 };
 const vec3 = v => (Array.isArray(v) ? [Number(v[0]), Number(v[1]), Number(v[2])] : [Number(v.x), Number(v.y), Number(v.z)]);
 const COMPARE = { lt: 0, lte: 1, gt: 2, gte: 3, eq: 4, neq: 5 };
 const normaliseActions = actions => actions.map((a) => {
@@ -287,6 +288,13 @@ const normaliseActions = actions => actions.map((a) => {
                 { k: ACTION.decimate, mode: 1, amount: Number(a.fraction) };
         case 'orderByImportance':
             return { k: ACTION.orderByImportance };
+        case 'filterOutliers': {  // mode 0: sigma, 1: distance (st_outlier_mode); a k that is no integer: 0, refused
+            const k = a.k === undefined ? 8 : Number(a.k);
+            const neighbors = Number.isInteger(k) && Math.abs(k) < 2 ** 31 ? k : 0;
+            return a.distance === undefined ?
+                { k: ACTION.filterOutliers, neighbors, mode: 0, amount: Number(a.sigma) } :
+                { k: ACTION.filterOutliers, neighbors, mode: 1, amount: Number(a.distance) };
+        }
         default:
             return { k: 0 };  // unknown kinds: the reference's switch ignores them
     }
@@ -319,7 +327,7 @@ const processSchema = (dataTable, actions) => {
 // input arrays, the rest runs on the mutated table.
 const isTransform = a => a.kind === 'translate' || a.kind === 'rotate' || a.kind === 'scale';
 const isFilter = a => a.kind === 'filterNaN' || a.kind === 'filterByValue' || a.kind === 'filterBox' ||
-    a.kind === 'filterSphere' || a.kind === 'decimate' || a.kind === 'orderByImportance';
+    a.kind === 'filterSphere' || a.kind === 'decimate' || a.kind === 'orderByImportance' || a.kind === 'filterOutliers';
 const processDataTable = (dataTable, processActions) => {
     const cols = () => dataTable.columns.map(c => c.data);
     const names = dataTable.columns.map(c => c.name);

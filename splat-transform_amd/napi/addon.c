@@ -628,6 +628,11 @@ static int parse_actions(napi_env env, napi_value actions, chain_args *a) {
             x->amount_mode = (int32_t)prop_num(env, o, "mode");
             x->amount = prop_num(env, o, "amount");
         }
+        if (x->kind == ST_ACTION_FILTER_OUTLIERS) {
+            x->neighbors = (int32_t)prop_num(env, o, "neighbors");
+            x->outlier_mode = (int32_t)prop_num(env, o, "mode");
+            x->outlier_value = prop_num(env, o, "amount");
+        }
         if (x->kind == ST_ACTION_TRANSFORM) {
             double t[3], r[4];
             napi_value tv, rv, e;

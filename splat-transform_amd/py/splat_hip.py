@@ -64,12 +64,15 @@ class Action(ctypes.Structure):
     _fields_ = [('kind', ctypes.c_int32), ('compare', ctypes.c_int32), ('column', ctypes.c_char_p),
                 ('value', ctypes.c_double), ('bands', ctypes.c_int32), ('transform', TransformParams),
                 ('box_min', ctypes.c_double * 3), ('box_max', ctypes.c_double * 3), ('center', ctypes.c_double * 3),
-                ('radius', ctypes.c_double), ('amount', ctypes.c_double), ('amount_mode', ctypes.c_int32)]
+                ('radius', ctypes.c_double), ('amount', ctypes.c_double), ('amount_mode', ctypes.c_int32),
+                ('neighbors', ctypes.c_int32), ('outlier_mode', ctypes.c_int32), ('outlier_value', ctypes.c_double)]
 
 
 ACTION_TRANSFORM, ACTION_FILTER_NAN, ACTION_FILTER_VALUE, ACTION_FILTER_BANDS, ACTION_PARAM = 1, 2, 3, 4, 5
 ACTION_ORDER_IMPORTANCE, ACTION_DECIMATE, ACTION_FILTER_BOX, ACTION_FILTER_SPHERE = 6, 7, 8, 9
+ACTION_FILTER_OUTLIERS = 10
 DECIMATE_COUNT, DECIMATE_FRACTION = 0, 1
+OUTLIER_SIGMA, OUTLIER_DISTANCE = 0, 1
 COMPARE = {'lt': 0, 'lte': 1, 'gt': 2, 'gte': 3, 'eq': 4, 'neq': 5}
 
 
@@ -147,6 +150,7 @@ EXPORTS = [
     'st_dev_spz_gz_read',
     'st_dev_summary', 'st_summary', 'st_summary_text', 'st_ctx_last_summary_stats',
     'st_dev_importance', 'st_dev_importance_order', 'st_dev_importance_top',
+    'st_dev_neighbor_dist', 'st_ctx_last_neighbor_stats',
     'st_dev_probe',
 ]
 
@@ -175,6 +179,7 @@ def lib():
         L.st_ctx_last_timings.restype = ctypes.c_char_p
         L.st_ctx_last_kmeans_stats.restype = ctypes.c_char_p
         L.st_ctx_last_summary_stats.restype = ctypes.c_char_p
+        L.st_ctx_last_neighbor_stats.restype = ctypes.c_char_p
         L.st_ctx_destroy.restype = None
         L.st_comm_destroy.restype = None
         L.st_group_destroy.restype = None
@@ -193,7 +198,7 @@ def lib():
             getattr(L, name).argtypes = [ctypes.c_uint64]
         for name in EXPORTS:
             if name not in ('st_last_error', 'st_ctx_last_timings', 'st_ctx_last_kmeans_stats',
-                            'st_ctx_last_summary_stats', 'st_ctx_destroy', 'st_free', 'st_webp_max_size',
+                            'st_ctx_last_summary_stats', 'st_ctx_last_neighbor_stats', 'st_ctx_destroy', 'st_free', 'st_webp_max_size',
                             'st_ply_row_bytes', 'st_csv_max_row_bytes', 'st_base64_size', 'st_comm_destroy',
                             'st_group_destroy', 'st_spz_image_size', 'st_ksplat_image_size', 'st_deflate_bound',
                             'st_gzip_bound'):
@@ -464,7 +469,8 @@ def make_actions(actions):
     translate / rotate / scale (value as in action_params), filterNaN, filterByValue (columnName,
     comparator, value), filterBands (value), param; and this project's own (st_abi.h, "importance,
     decimation and crops"): filterBox (min, max: three numbers each), filterSphere (center, radius),
-    decimate (count or fraction), orderByImportance"""
+    decimate (count or fraction), orderByImportance; and ("neighbour distances and outliers")
+    filterOutliers (k, default 8, and either sigma or distance)"""
     arr = (Action * max(1, len(actions)))()
     keep = []
     for a, act in zip(arr, actions):
@@ -494,6 +500,13 @@ def make_actions(actions):
             a.amount = float(act['count'] if 'count' in act else act['fraction'])
         elif k == 'orderByImportance':
             a.kind = ACTION_ORDER_IMPORTANCE
+        elif k == 'filterOutliers':
+            if ('sigma' in act) == ('distance' in act):
+                raise ValueError('filterOutliers takes either sigma or distance')
+            kk = act.get('k', 8)
+            a.kind, a.neighbors = ACTION_FILTER_OUTLIERS, (int(kk) if int(kk) == kk and abs(kk) < 2 ** 31 else 0)  # 0: refused
+            a.outlier_mode = OUTLIER_SIGMA if 'sigma' in act else OUTLIER_DISTANCE
+            a.outlier_value = float(act['sigma'] if 'sigma' in act else act['distance'])
         else:
             raise ValueError(k)
     arr._keep = keep
@@ -523,8 +536,9 @@ def process_schema(items, actions, with_source=False):
 
 
 TRANSFORM_KINDS = ('translate', 'rotate', 'scale')
-# the kinds that copy the table (the four after filterByValue are this project's own)
-FILTER_KINDS = ('filterNaN', 'filterByValue', 'filterBox', 'filterSphere', 'decimate', 'orderByImportance')
+# the kinds that copy the table (those after filterByValue are this project's own)
+FILTER_KINDS = ('filterNaN', 'filterByValue', 'filterBox', 'filterSphere', 'decimate', 'orderByImportance',
+                'filterOutliers')
 
 
 def sog_geometry(n, sh_coeffs):
@@ -1195,6 +1209,26 @@ class Context:
     def importance_order(self, cols):
         """the importance order of host columns (numpy arrays), uploaded -> uint32 array"""
         return self.dev_importance_order(self._upload(cols)).cpu().numpy().view(np.uint32)
+
+    def dev_neighbor_dist(self, cols, k):
+        """st_dev_neighbor_dist: the distance from every row of device columns (list of (name, tensor)
+        or a dict; x, y, z of any of the eight types) to its k-th nearest other placed row (st_abi.h,
+        "neighbour distances and outliers") -> float64 tensor"""
+        import torch
+        t = make_ttable(cols)
+        out = torch.empty(t.n, dtype=torch.float64, device=f'cuda:{self.device}')
+        check(lib().st_dev_neighbor_dist(self.h, ctypes.byref(t), ctypes.c_int32(int(k)), _ptr(out)))
+        return out
+
+    def neighbor_dist(self, cols, k):
+        """the same of host columns (numpy arrays), uploaded -> float64 array"""
+        return self.dev_neighbor_dist(self._upload(cols), k).cpu().numpy()
+
+    def last_neighbor_stats(self):
+        """the last neighbour search's sizes and work (st_ctx_last_neighbor_stats) as a dict: rows,
+        placed, leaves, levels, pairs (d2 evaluations), nodes (box tests)"""
+        import json
+        return json.loads(lib().st_ctx_last_neighbor_stats(self.h).decode())
 
     def summary_stats(self):
         """the last summary's sum paths (st_ctx_last_summary_stats) as a dict: columns, fast, general,
