@@ -308,11 +308,14 @@ enum st_action_kind {
     /* this project's own kinds: "importance, decimation and crops" below */
     ST_ACTION_ORDER_IMPORTANCE, ST_ACTION_DECIMATE, ST_ACTION_FILTER_BOX, ST_ACTION_FILTER_SPHERE,
     /* "neighbour distances and outliers" below */
-    ST_ACTION_FILTER_OUTLIERS
+    ST_ACTION_FILTER_OUTLIERS,
+    /* "clusters" below */
+    ST_ACTION_FILTER_CLUSTERS
 };
 enum st_compare { ST_CMP_LT = 0, ST_CMP_LTE, ST_CMP_GT, ST_CMP_GTE, ST_CMP_EQ, ST_CMP_NEQ };
 enum st_decimate_mode { ST_DECIMATE_COUNT = 0, ST_DECIMATE_FRACTION = 1 };
 enum st_outlier_mode { ST_OUTLIER_SIGMA = 0, ST_OUTLIER_DISTANCE = 1 };
+enum st_cluster_mode { ST_CLUSTER_MIN_SIZE = 0, ST_CLUSTER_LARGEST = 1 };
 typedef struct {
     int32_t kind;                    /* st_action_kind */
     int32_t compare;                 /* ST_ACTION_FILTER_VALUE: st_compare */
@@ -329,6 +332,9 @@ typedef struct {
     int32_t neighbors;               /* ST_ACTION_FILTER_OUTLIERS: k, 1..32 */
     int32_t outlier_mode;            /* ST_ACTION_FILTER_OUTLIERS: st_outlier_mode */
     double outlier_value;            /* ST_ACTION_FILTER_OUTLIERS: sigma, or the distance */
+    double cluster_radius;           /* ST_ACTION_FILTER_CLUSTERS: the link radius, >= 0 (+Infinity allowed) */
+    int32_t cluster_mode;            /* ST_ACTION_FILTER_CLUSTERS: st_cluster_mode */
+    double cluster_min;              /* ST_ACTION_FILTER_CLUSTERS, ST_CLUSTER_MIN_SIZE: the smallest size kept */
 } st_action;
 int st_process(st_ctx *ctx, const st_ttable *src, const st_action *actions, int32_t nactions, const st_ttable *dst,
                uint64_t *out_m);
@@ -1329,6 +1335,59 @@ int st_dev_importance_top(st_ctx *ctx, const st_ttable *dev_table, uint64_t m, u
  * levels, leaves to root), "pairs" (d2 evaluations), "nodes" (box tests)}. */
 int st_dev_neighbor_dist(st_ctx *ctx, const st_ttable *dev_table, int32_t k, double *dev_dist);
 const char *st_ctx_last_neighbor_stats(st_ctx *ctx);
+
+/* ---- clusters -----------------------------------------------------------------------------------------
+ * Cleaning a scene, second tool: floaters rarely come alone, and a clump of them has an ordinary
+ * dist_k, because every member's neighbours are inside the clump.  Connectivity finds it: link every
+ * two rows closer than a radius, keep the connected components that are large, or only the largest.
+ * The reference has no such command (its kd-tree answers nearest-one queries only), so the rules are
+ * this project's own, in the style of the two sections above: a result depends only on the data --
+ * not on the order of the rows, the shape of a launch, the search tree or the order in which atomics
+ * arrive -- and is checked bit for bit against a brute-force serial form.  csrc/st_clusters.h holds
+ * every rule as a host/device function and that serial form.
+ *
+ * Every value is the column's element as a JS number (any st_ply_type, widened exactly); all
+ * arithmetic is IEEE double, each operation rounds once in the order written, nothing is fused.
+ *   placed, d2  those of "neighbour distances and outliers", unchanged.  A table without an x, y or z
+ *              column is ST_ERR_ARG (the message names the column); nothing is launched.
+ *   radius     any double >= 0, +Infinity included; NaN or a negative value is ST_ERR_ARG before any
+ *              launch.  r2 = radius * radius, one multiplication; it may be +Infinity.
+ *   link(i, j) iff i != j, both rows are placed and d2(i, j) <= r2.  Inclusive: a pair at exactly the
+ *              radius links.  Symmetric bit for bit: x_i - x_j and x_j - x_i are exact negations, so
+ *              their squares are equal.  r2 = +Infinity links every two placed rows, pairs whose d2
+ *              overflowed included; radius = 0 links exactly the rows that coincide.
+ *   component  the connected components of the link graph over the placed rows.  label(i) is the
+ *              smallest row index in row i's component, 0xFFFFFFFF for a row that is not placed;
+ *              size(i) is the number of rows of the component, 0 for a row that is not placed.  The
+ *              partition is a property of the data; the labels additionally depend on the numbering
+ *              of the rows, by definition.
+ *   ST_ACTION_FILTER_CLUSTERS (filterClusters)   cluster_radius = radius.  cluster_mode
+ *              ST_CLUSTER_MIN_SIZE keeps row i iff it is placed and size(i) >= cluster_min;
+ *              cluster_min must be a finite, non-negative, integer-valued double below 2^53, as
+ *              decimate's count (ST_ERR_ARG otherwise).  ST_CLUSTER_LARGEST keeps every row whose
+ *              component has the maximal size; several components may tie for it and all of them are
+ *              kept, so the kept set never depends on the numbering of the rows (cluster_min is not
+ *              read).  Another mode is ST_ERR_ARG.  Rows that are not placed go.  A stable selection
+ *              through permuteRows, like the filters; all rows kept: the table stays as it is; n = 0
+ *              does nothing; no placed row: nothing is kept.
+ * The action is global: st_group_sog_bundle_process refuses it with ST_ERR_UNSUPPORTED before any
+ * rank uploads, as it does ST_ACTION_FILTER_OUTLIERS.  (The st_set_devices group of the one-call forms
+ * runs the actions on one device first: it works there.)
+ *
+ * st_dev_clusters: dev_label[i] = label(i) and dev_size[i] = size(i) for a device table of n < 2^32
+ * rows (ST_ERR_UNSUPPORTED above), columns aligned to their types, the outputs to 4 bytes; either
+ * output may be NULL.  It works on the context stream and waits for it.  The search runs over the
+ * tree of st_dev_neighbor_dist (ST_KNN_LEAF sets L for both): one wave takes a leaf as its queries,
+ * prunes a node when the lower bound of d2 is > r2 for every one of them, and takes a whole node at
+ * once, without one d2, where the node is a clique (the upper bound of d2 between two rows of its
+ * own box is <= r2) and the upper bound of d2 between the query and its box is <= r2 -- both bounds
+ * computed with d2's own operations in d2's order, so that no tolerance exists anywhere.  Linked rows
+ * are joined in a lock-free union-find that hooks the larger root under the smaller.
+ * st_ctx_last_cluster_stats: the last call's JSON -- {"rows", "placed", "components", "largest",
+ * "leaves", "levels" (box levels, leaves to root), "pairs" (d2 evaluations), "nodes" (box tests),
+ * "unions" (successful hooks)}. */
+int st_dev_clusters(st_ctx *ctx, const st_ttable *dev_table, double radius, uint32_t *dev_label, uint32_t *dev_size);
+const char *st_ctx_last_cluster_stats(st_ctx *ctx);
 
 /* ---- st_dev_probe: a test hook ----------------------------------------------------------------
  * The two layers under every bit-exact result, called directly so that tests can compare them

@@ -100,6 +100,7 @@ void run_actions(Chain &ch, const st_action *actions, int nactions) {
     // (filterOutliers alike: no action adds or removes a position column)
     for (int a = 0; a < nactions; ++a) {
         if (actions[a].kind == ST_ACTION_FILTER_OUTLIERS) outliers_require(ch.typed(), actions[a]);
+        if (actions[a].kind == ST_ACTION_FILTER_CLUSTERS) filter_clusters_require(ch.typed(), actions[a]);
         if (actions[a].kind != ST_ACTION_DECIMATE && actions[a].kind != ST_ACTION_ORDER_IMPORTANCE) continue;
         const bool dec = actions[a].kind == ST_ACTION_DECIMATE;
         importance_require(ch.typed(), dec ? "decimate" : "orderByImportance");
@@ -177,6 +178,14 @@ void run_actions(Chain &ch, const st_action *actions, int nactions) {
                 if (ch.n == 0) break;
                 auto *idx = wsT<uint32_t>(ch.c, ch.tag + ".idx", ch.n);
                 const uint64_t m = filter_outliers_tdev(ch.c, ch.typed(), act, ch.tag, idx);
+                if (m != ch.n) ch.gather(idx, m);
+                break;
+            }
+            // st_abi.h, "clusters": the sizes of the link graph's components, a stable selection
+            case ST_ACTION_FILTER_CLUSTERS: {
+                if (ch.n == 0) break;
+                auto *idx = wsT<uint32_t>(ch.c, ch.tag + ".idx", ch.n);
+                const uint64_t m = filter_clusters_tdev(ch.c, ch.typed(), act, ch.tag, idx);
                 if (m != ch.n) ch.gather(idx, m);
                 break;
             }

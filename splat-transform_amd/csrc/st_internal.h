@@ -156,6 +156,8 @@ struct st_ctx {
     std::string last_summary_stats = "{}";
     // the last neighbour search's sizes and work (st_ctx_last_neighbor_stats)
     std::string last_neighbor_stats = "{}";
+    // the last cluster search's sizes and work (st_ctx_last_cluster_stats)
+    std::string last_cluster_stats = "{}";
     // kernel profiling (st_ctx_set_profiling)
     bool profiling = false;
     struct KEv {
@@ -353,6 +355,18 @@ void neighbors_require(const st_ttable *t, int32_t k, const char *what);
 void outliers_require(const st_ttable *t, const st_action &act);
 void neighbor_dist_tdev(st_ctx *c, const st_ttable *t, int32_t k, const std::string &tag, double *dist);
 uint64_t filter_outliers_tdev(st_ctx *c, const st_ttable *t, const st_action &act, const std::string &tag,
+                              uint32_t *out_idx);
+// clusters (st_clusters.hip; the rules: st_clusters.h), over the same tree (st_nbtree.h).  Workspace
+// slots go under `tag`.  clusters_require: ST_ERR_ARG unless t has x, y and z and the radius is >= 0
+// (no launch); filter_clusters_require: that, and the action's mode and minimum.  clusters_tdev:
+// label and size of every row (n uint32 each, either may be null); it waits for the stream, leaves
+// st_ctx_last_cluster_stats and returns the largest size.  filter_clusters_tdev: the kept rows
+// ascending into out_idx, their count returned (sync)
+void clusters_require(const st_ttable *t, double radius, const char *what);
+void filter_clusters_require(const st_ttable *t, const st_action &act);
+uint32_t clusters_tdev(st_ctx *c, const st_ttable *t, double radius, const std::string &tag, uint32_t *label,
+                       uint32_t *size);
+uint64_t filter_clusters_tdev(st_ctx *c, const st_ttable *t, const st_action &act, const std::string &tag,
                               uint32_t *out_idx);
 int combine_layout(const st_ttable *const *srcs, int nsrc, int32_t *col_table, int32_t *col_index);
 void combine_tdev(st_ctx *c, const st_ttable *const *srcs, int nsrc, const st_ttable *dst);

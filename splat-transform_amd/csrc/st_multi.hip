@@ -1284,6 +1284,9 @@ static uint64_t group_sog(st_group *g, const st_table *const *tabs, int ntab, co
             // a row's neighbours may lie in another rank's slice
             ST_REQUIRE(actions[t][a].kind != ST_ACTION_FILTER_OUTLIERS, ST_ERR_UNSUPPORTED,
                        "group: filterOutliers needs the whole table on one device");
+            // a component may run through every rank's slice
+            ST_REQUIRE(actions[t][a].kind != ST_ACTION_FILTER_CLUSTERS, ST_ERR_UNSUPPORTED,
+                       "group: filterClusters needs the whole table on one device");
         }
     std::vector<uint64_t> used(world, 0);
     g->run([&](int r) {

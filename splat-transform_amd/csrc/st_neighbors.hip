@@ -25,33 +25,27 @@
 //   k_nb_flags     keep iff dist <= t, t from the summary's mean and std_dev read on the host
 // Nothing here depends on the order in which atomics arrive: the atomics are integer minima, maxima
 // and counts.  Workspace slots carry the caller's tag.
+// The build -- extent, keys, sort, gather, leaf boxes and levels -- is nbt::build_tree (st_nbtree.h):
+// st_clusters.hip searches the same tree.
 #include <cstdlib>
 #include <cstring>
 
 #include "st_internal.h"
+#include "st_nbtree.h"
 #include "st_neighbors.h"
 
 namespace st {
 namespace {
 
 using namespace nbr;
+using namespace nbt;
 typedef unsigned long long ull;
 
 constexpr int SEED = 1;          // leaves scanned either side of the wave's own before the walk
-constexpr int MAX_LEVELS = 12;   // leaves <= 2^30 (n < 2^32, L >= 4): at most 11 levels
-constexpr int STACK = 7 * MAX_LEVELS + 8;
 
-struct NCols {  // kernel argument: x, y, z of any type
-    const void *p[3];
-    int32_t type[3];
-};
 struct Extent {  // device record of k_nb_extent
     ull lo[3], hi[3];  // sm::key_of(ST_PLY_DOUBLE) of the extremes
     ull placed;
-};
-struct Tree {  // kernel argument: level l's boxes are box[off[l] .. off[l] + cnt[l]) (six doubles each)
-    uint32_t off[MAX_LEVELS], cnt[MAX_LEVELS];
-    int levels;
 };
 struct Counters {
     ull pairs, nodes;
@@ -270,6 +264,57 @@ __global__ __launch_bounds__(256) void k_nb_flags(const double *__restrict__ dis
         flags[i] = keep(dist[i], t) ? 1u : 0u;
 }
 
+struct Stats {
+    uint64_t rows = 0, placed = 0, leaves = 0, levels = 0, pairs = 0, nodes = 0;
+};
+void publish(st_ctx *c, const Stats &s) {
+    c->last_neighbor_stats = "{\"rows\": " + std::to_string(s.rows) + ", \"placed\": " + std::to_string(s.placed) +
+                             ", \"leaves\": " + std::to_string(s.leaves) + ", \"levels\": " + std::to_string(s.levels) +
+                             ", \"pairs\": " + std::to_string(s.pairs) + ", \"nodes\": " + std::to_string(s.nodes) + "}";
+}
+
+template <typename T4>
+void gather_and_boxes(st_ctx *c, const NCols &cs, const std::string &tag, Built &T) {
+    auto *pos = wsT<T4>(c, tag + ".nb.pos", T.P);
+    T.pos = pos;
+    {
+        KTimer kt(c, "nb.gather");
+        hipLaunchKernelGGL(k_nb_gather<T4>, dim3(grid_for(T.P, 256, 8192)), dim3(256), 0, c->stream, cs,
+                           (const uint32_t *)T.order, T.P, pos);
+        ST_LAUNCH_CHECK();
+    }
+    {
+        KTimer kt(c, "nb.boxes");
+        const Tree &tr = T.tr;
+        hipLaunchKernelGGL(k_nb_leaves<T4>, dim3(grid_for(tr.cnt[0], 256)), dim3(256), 0, c->stream, (const T4 *)pos, T.P,
+                           T.L, tr.cnt[0], T.box);
+        ST_LAUNCH_CHECK();
+        for (int l = 1; l < tr.levels; ++l) {
+            hipLaunchKernelGGL(k_nb_level, dim3(grid_for(tr.cnt[l], 256)), dim3(256), 0, c->stream,
+                               (const double *)(T.box + (uint64_t)tr.off[l - 1] * 6), tr.cnt[l - 1],
+                               T.box + (uint64_t)tr.off[l] * 6, tr.cnt[l]);
+            ST_LAUNCH_CHECK();
+        }
+    }
+}
+
+template <typename T4>
+void search(st_ctx *c, const Built &T, int k, double *dist, Counters *d_cnt) {
+    KTimer kt(c, "nb.search");
+    const dim3 g(T.tr.cnt[0]);
+    if (k <= 8)
+        hipLaunchKernelGGL((k_nb_search<T4, 8>), g, dim3(64), 0, c->stream, (const T4 *)T.pos, (const uint32_t *)T.order,
+                           T.P, T.L, k, (const double *)T.box, T.tr, dist, d_cnt);
+    else
+        hipLaunchKernelGGL((k_nb_search<T4, K_MAX>), g, dim3(64), 0, c->stream, (const T4 *)T.pos,
+                           (const uint32_t *)T.order, T.P, T.L, k, (const double *)T.box, T.tr, dist, d_cnt);
+    ST_LAUNCH_CHECK();
+}
+
+}  // namespace
+
+namespace nbt {
+
 const char *const XYZ[3] = {"x", "y", "z"};
 
 NCols xyz_cols(const st_ttable *t, const char *what) {
@@ -295,22 +340,39 @@ int leaf_size() {  // read per call (tests set it around one call)
     return LEAF_DEFAULT;
 }
 
-struct Stats {
-    uint64_t rows = 0, placed = 0, leaves = 0, levels = 0, pairs = 0, nodes = 0;
-};
-void publish(st_ctx *c, const Stats &s) {
-    c->last_neighbor_stats = "{\"rows\": " + std::to_string(s.rows) + ", \"placed\": " + std::to_string(s.placed) +
-                             ", \"leaves\": " + std::to_string(s.leaves) + ", \"levels\": " + std::to_string(s.levels) +
-                             ", \"pairs\": " + std::to_string(s.pairs) + ", \"nodes\": " + std::to_string(s.nodes) + "}";
-}
-
-template <typename T4>
-void build_and_search(st_ctx *c, const NCols &cs, const uint32_t *order, uint64_t P, int L, int k,
-                      const std::string &tag, double *dist, Counters *d_cnt, Stats &S) {
-    auto *pos = wsT<T4>(c, tag + ".nb.pos", P);
-    Tree tr{};
+void build_tree(st_ctx *c, const NCols &cs, uint64_t n, const std::string &tag, Built &T) {
+    T = Built{};
+    T.L = leaf_size();
+    auto *ex = wsT<Extent>(c, tag + ".nb.extent", 1);
+    auto *h = static_cast<Extent *>(pinned_slot(c, "nb.host.extent", 2 * sizeof(Extent)));
+    Extent *h_ex0 = h, *h_ex = h + 1;  // what goes up, what comes back
+    *h_ex0 = Extent{{~0ull, ~0ull, ~0ull}, {0, 0, 0}, 0};
+    ST_HIP(hipMemcpyAsync(ex, h_ex0, sizeof(Extent), hipMemcpyHostToDevice, c->stream));
+    {
+        KTimer kt(c, "nb.extent");
+        hipLaunchKernelGGL(k_nb_extent, dim3(grid_for(n, 256 * 8, 2048)), dim3(256), 0, c->stream, cs, n, ex);
+        ST_LAUNCH_CHECK();
+    }
+    ST_HIP(hipMemcpyAsync(h_ex, ex, sizeof(Extent), hipMemcpyDeviceToHost, c->stream));
+    auto *keys = wsT<uint32_t>(c, tag + ".nb.keys", n);
+    auto *skeys = wsT<uint32_t>(c, tag + ".nb.skeys", n);
+    T.order = wsT<uint32_t>(c, tag + ".nb.order", n);
+    {
+        KTimer kt(c, "nb.keys");
+        hipLaunchKernelGGL(k_nb_keys, dim3(grid_for(n, 256, 8192)), dim3(256), 0, c->stream, cs, n, (const Extent *)ex, keys);
+        ST_LAUNCH_CHECK();
+    }
+    {
+        KTimer kt(c, "nb.sort");
+        radix_sort_u32_iota(c, keys, n, 0, 32, skeys, T.order, tag + ".nb.sort");
+    }
+    ST_HIP(hipStreamSynchronize(c->stream));
+    T.P = h_ex->placed;
+    ST_REQUIRE(T.P <= n, ST_ERR_INTERNAL, "neighbors: more placed rows than rows");
+    if (!T.P) return;
+    Tree &tr = T.tr;
     uint64_t total = 0;
-    uint64_t cnt = (P + L - 1) / L;
+    uint64_t cnt = (T.P + T.L - 1) / T.L;
     for (;;) {
         ST_REQUIRE(tr.levels < MAX_LEVELS, ST_ERR_INTERNAL, "neighbors: too many tree levels");
         tr.off[tr.levels] = (uint32_t)total;
@@ -321,40 +383,14 @@ void build_and_search(st_ctx *c, const NCols &cs, const uint32_t *order, uint64_
         cnt = (cnt + 7) / 8;
     }
     ST_REQUIRE(total < (1ull << 32), ST_ERR_INTERNAL, "neighbors: too many tree nodes");
-    auto *box = wsT<double>(c, tag + ".nb.box", total * 6);
-    {
-        KTimer kt(c, "nb.gather");
-        hipLaunchKernelGGL(k_nb_gather<T4>, dim3(grid_for(P, 256, 8192)), dim3(256), 0, c->stream, cs, order, P, pos);
-        ST_LAUNCH_CHECK();
-    }
-    {
-        KTimer kt(c, "nb.boxes");
-        hipLaunchKernelGGL(k_nb_leaves<T4>, dim3(grid_for(tr.cnt[0], 256)), dim3(256), 0, c->stream, (const T4 *)pos, P, L,
-                           tr.cnt[0], box);
-        ST_LAUNCH_CHECK();
-        for (int l = 1; l < tr.levels; ++l) {
-            hipLaunchKernelGGL(k_nb_level, dim3(grid_for(tr.cnt[l], 256)), dim3(256), 0, c->stream,
-                               (const double *)(box + (uint64_t)tr.off[l - 1] * 6), tr.cnt[l - 1],
-                               box + (uint64_t)tr.off[l] * 6, tr.cnt[l]);
-            ST_LAUNCH_CHECK();
-        }
-    }
-    {
-        KTimer kt(c, "nb.search");
-        const dim3 g(tr.cnt[0]);
-        if (k <= 8)
-            hipLaunchKernelGGL((k_nb_search<T4, 8>), g, dim3(64), 0, c->stream, (const T4 *)pos, order, P, L, k,
-                               (const double *)box, tr, dist, d_cnt);
-        else
-            hipLaunchKernelGGL((k_nb_search<T4, K_MAX>), g, dim3(64), 0, c->stream, (const T4 *)pos, order, P, L, k,
-                               (const double *)box, tr, dist, d_cnt);
-        ST_LAUNCH_CHECK();
-    }
-    S.leaves = tr.cnt[0];
-    S.levels = (uint64_t)tr.levels;
+    T.nodes = total;
+    T.box = wsT<double>(c, tag + ".nb.box", total * 6);
+    T.f32 = cs.type[0] == ST_PLY_FLOAT && cs.type[1] == ST_PLY_FLOAT && cs.type[2] == ST_PLY_FLOAT;
+    if (T.f32) gather_and_boxes<float4>(c, cs, tag, T);
+    else gather_and_boxes<double4>(c, cs, tag, T);
 }
 
-}  // namespace
+}  // namespace nbt
 
 void neighbors_require(const st_ttable *t, int32_t k, const char *what) {
     (void)xyz_cols(t, what);
@@ -380,49 +416,25 @@ void neighbor_dist_tdev(st_ctx *c, const st_ttable *t, int32_t k, const std::str
         publish(c, S);
         return;
     }
-    const int L = leaf_size();
-    auto *ex = wsT<Extent>(c, tag + ".nb.extent", 1);
     auto *d_cnt = wsT<Counters>(c, tag + ".nb.counters", 1);
-    auto *h = static_cast<char *>(pinned_slot(c, "nb.host", 2 * sizeof(Extent) + sizeof(Counters)));
-    auto *h_ex0 = reinterpret_cast<Extent *>(h), *h_ex = h_ex0 + 1;  // what goes up, what comes back
-    auto *h_cnt = reinterpret_cast<Counters *>(h + 2 * sizeof(Extent));
-    *h_ex0 = Extent{{~0ull, ~0ull, ~0ull}, {0, 0, 0}, 0};
-    ST_HIP(hipMemcpyAsync(ex, h_ex0, sizeof(Extent), hipMemcpyHostToDevice, c->stream));
+    auto *h_cnt = static_cast<Counters *>(pinned_slot(c, "nb.host", sizeof(Counters)));
     ST_HIP(hipMemsetAsync(d_cnt, 0, sizeof(Counters), c->stream));
     {
         KTimer kt(c, "nb.fill");
         hipLaunchKernelGGL(k_nb_fill, dim3(grid_for(n, 256, 8192)), dim3(256), 0, c->stream, dist, n);
         ST_LAUNCH_CHECK();
     }
-    {
-        KTimer kt(c, "nb.extent");
-        hipLaunchKernelGGL(k_nb_extent, dim3(grid_for(n, 256 * 8, 2048)), dim3(256), 0, c->stream, cs, n, ex);
-        ST_LAUNCH_CHECK();
-    }
-    ST_HIP(hipMemcpyAsync(h_ex, ex, sizeof(Extent), hipMemcpyDeviceToHost, c->stream));
-    auto *keys = wsT<uint32_t>(c, tag + ".nb.keys", n);
-    auto *skeys = wsT<uint32_t>(c, tag + ".nb.skeys", n);
-    auto *order = wsT<uint32_t>(c, tag + ".nb.order", n);
-    {
-        KTimer kt(c, "nb.keys");
-        hipLaunchKernelGGL(k_nb_keys, dim3(grid_for(n, 256, 8192)), dim3(256), 0, c->stream, cs, n, (const Extent *)ex, keys);
-        ST_LAUNCH_CHECK();
-    }
-    {
-        KTimer kt(c, "nb.sort");
-        radix_sort_u32_iota(c, keys, n, 0, 32, skeys, order, tag + ".nb.sort");
-    }
-    ST_HIP(hipStreamSynchronize(c->stream));
-    const uint64_t P = h_ex->placed;
-    ST_REQUIRE(P <= n, ST_ERR_INTERNAL, "neighbor_dist: more placed rows than rows");
-    S.placed = P;
-    if (P) {
-        const bool f32 = cs.type[0] == ST_PLY_FLOAT && cs.type[1] == ST_PLY_FLOAT && cs.type[2] == ST_PLY_FLOAT;
-        if (f32) build_and_search<float4>(c, cs, order, P, L, k, tag, dist, d_cnt, S);
-        else build_and_search<double4>(c, cs, order, P, L, k, tag, dist, d_cnt, S);
+    Built T;
+    build_tree(c, cs, n, tag, T);
+    S.placed = T.P;
+    if (T.P) {
+        if (T.f32) search<float4>(c, T, k, dist, d_cnt);
+        else search<double4>(c, T, k, dist, d_cnt);
         ST_HIP(hipMemcpyAsync(h_cnt, d_cnt, sizeof(Counters), hipMemcpyDeviceToHost, c->stream));
         ST_HIP(hipStreamSynchronize(c->stream));
         S.pairs = h_cnt->pairs, S.nodes = h_cnt->nodes;
+        S.leaves = T.tr.cnt[0];
+        S.levels = (uint64_t)T.tr.levels;
     }
     publish(c, S);
 }

@@ -253,9 +253,11 @@ const packCompressed = (dataTable) => {
 // This project's own kinds (st_abi.h, "importance, decimation and crops"): filterBox {min, max},
 // filterSphere {center, radius}, decimate {count} or {fraction}, orderByImportance; a point is a Vec3
 // or an array of three numbers.  And ("neighbour distances and outliers") filterOutliers {k, sigma} or
-// {k, distance}; k defaults to 8.
+// {k, distance}; k defaults to 8.  And ("clusters") filterClusters {radius, minSize} or {radius, keep:
+// 'largest'}.
 const ACTION = { transform: 1, filterNaN: 2, filterByValue: 3, filterBands: 4, param: 5,
-    orderByImportance: 6, decimate: 7, filterBox: 8, filterSphere: 9, filterOutliers: 10 };
+    orderByImportance: 6, decimate: 7, filterBox: 8, filterSphere: 9, filterOutliers: 10,
+    filterClusters: 11 };
 const vec3 = v => (Array.isArray(v) ? [Number(v[0]), Number(v[1]), Number(v[2])] : [Number(v.x), Number(v.y), Number(v.z)]);
 const COMPARE = { lt: 0, lte: 1, gt: 2, gte: 3, eq: 4, neq: 5 };
 const normaliseActions = actions => actions.map((a) => {
@@ -295,6 +297,11 @@ const normaliseActions = actions => actions.map((a) => {
                 { k: ACTION.filterOutliers, neighbors, mode: 0, amount: Number(a.sigma) } :
                 { k: ACTION.filterOutliers, neighbors, mode: 1, amount: Number(a.distance) };
         }
+        case 'filterClusters': {  // mode 0: minSize, 1: largest (st_cluster_mode); both or neither, or another keep: -1, refused
+            const largest = a.keep !== undefined, sized = a.minSize !== undefined;
+            const mode = largest === sized || (largest && a.keep !== 'largest') ? -1 : (largest ? 1 : 0);
+            return { k: ACTION.filterClusters, radius: Number(a.radius), mode, amount: sized ? Number(a.minSize) : 0 };
+        }
         default:
             return { k: 0 };  // unknown kinds: the reference's switch ignores them
     }
@@ -327,7 +334,8 @@ const processSchema = (dataTable, actions) => {
 // input arrays, the rest runs on the mutated table.
 const isTransform = a => a.kind === 'translate' || a.kind === 'rotate' || a.kind === 'scale';
 const isFilter = a => a.kind === 'filterNaN' || a.kind === 'filterByValue' || a.kind === 'filterBox' ||
-    a.kind === 'filterSphere' || a.kind === 'decimate' || a.kind === 'orderByImportance' || a.kind === 'filterOutliers';
+    a.kind === 'filterSphere' || a.kind === 'decimate' || a.kind === 'orderByImportance' || a.kind === 'filterOutliers' ||
+    a.kind === 'filterClusters';
 const processDataTable = (dataTable, processActions) => {
     const cols = () => dataTable.columns.map(c => c.data);
     const names = dataTable.columns.map(c => c.name);

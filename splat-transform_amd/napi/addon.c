@@ -633,6 +633,11 @@ static int parse_actions(napi_env env, napi_value actions, chain_args *a) {
             x->outlier_mode = (int32_t)prop_num(env, o, "mode");
             x->outlier_value = prop_num(env, o, "amount");
         }
+        if (x->kind == ST_ACTION_FILTER_CLUSTERS) {
+            x->cluster_radius = prop_num(env, o, "radius");
+            x->cluster_mode = (int32_t)prop_num(env, o, "mode");
+            x->cluster_min = prop_num(env, o, "amount");
+        }
         if (x->kind == ST_ACTION_TRANSFORM) {
             double t[3], r[4];
             napi_value tv, rv, e;

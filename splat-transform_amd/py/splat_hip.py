@@ -65,14 +65,17 @@ class Action(ctypes.Structure):
                 ('value', ctypes.c_double), ('bands', ctypes.c_int32), ('transform', TransformParams),
                 ('box_min', ctypes.c_double * 3), ('box_max', ctypes.c_double * 3), ('center', ctypes.c_double * 3),
                 ('radius', ctypes.c_double), ('amount', ctypes.c_double), ('amount_mode', ctypes.c_int32),
-                ('neighbors', ctypes.c_int32), ('outlier_mode', ctypes.c_int32), ('outlier_value', ctypes.c_double)]
+                ('neighbors', ctypes.c_int32), ('outlier_mode', ctypes.c_int32), ('outlier_value', ctypes.c_double),
+                ('cluster_radius', ctypes.c_double), ('cluster_mode', ctypes.c_int32), ('cluster_min', ctypes.c_double)]
 
 
 ACTION_TRANSFORM, ACTION_FILTER_NAN, ACTION_FILTER_VALUE, ACTION_FILTER_BANDS, ACTION_PARAM = 1, 2, 3, 4, 5
 ACTION_ORDER_IMPORTANCE, ACTION_DECIMATE, ACTION_FILTER_BOX, ACTION_FILTER_SPHERE = 6, 7, 8, 9
 ACTION_FILTER_OUTLIERS = 10
+ACTION_FILTER_CLUSTERS = 11
 DECIMATE_COUNT, DECIMATE_FRACTION = 0, 1
 OUTLIER_SIGMA, OUTLIER_DISTANCE = 0, 1
+CLUSTER_MIN_SIZE, CLUSTER_LARGEST = 0, 1
 COMPARE = {'lt': 0, 'lte': 1, 'gt': 2, 'gte': 3, 'eq': 4, 'neq': 5}
 
 
@@ -151,6 +154,7 @@ EXPORTS = [
     'st_dev_summary', 'st_summary', 'st_summary_text', 'st_ctx_last_summary_stats',
     'st_dev_importance', 'st_dev_importance_order', 'st_dev_importance_top',
     'st_dev_neighbor_dist', 'st_ctx_last_neighbor_stats',
+    'st_dev_clusters', 'st_ctx_last_cluster_stats',
     'st_dev_probe',
 ]
 
@@ -180,6 +184,7 @@ def lib():
         L.st_ctx_last_kmeans_stats.restype = ctypes.c_char_p
         L.st_ctx_last_summary_stats.restype = ctypes.c_char_p
         L.st_ctx_last_neighbor_stats.restype = ctypes.c_char_p
+        L.st_ctx_last_cluster_stats.restype = ctypes.c_char_p
         L.st_ctx_destroy.restype = None
         L.st_comm_destroy.restype = None
         L.st_group_destroy.restype = None
@@ -198,7 +203,7 @@ def lib():
             getattr(L, name).argtypes = [ctypes.c_uint64]
         for name in EXPORTS:
             if name not in ('st_last_error', 'st_ctx_last_timings', 'st_ctx_last_kmeans_stats',
-                            'st_ctx_last_summary_stats', 'st_ctx_last_neighbor_stats', 'st_ctx_destroy', 'st_free', 'st_webp_max_size',
+                            'st_ctx_last_summary_stats', 'st_ctx_last_neighbor_stats', 'st_ctx_last_cluster_stats', 'st_ctx_destroy', 'st_free', 'st_webp_max_size',
                             'st_ply_row_bytes', 'st_csv_max_row_bytes', 'st_base64_size', 'st_comm_destroy',
                             'st_group_destroy', 'st_spz_image_size', 'st_ksplat_image_size', 'st_deflate_bound',
                             'st_gzip_bound'):
@@ -470,7 +475,8 @@ def make_actions(actions):
     comparator, value), filterBands (value), param; and this project's own (st_abi.h, "importance,
     decimation and crops"): filterBox (min, max: three numbers each), filterSphere (center, radius),
     decimate (count or fraction), orderByImportance; and ("neighbour distances and outliers")
-    filterOutliers (k, default 8, and either sigma or distance)"""
+    filterOutliers (k, default 8, and either sigma or distance); and ("clusters") filterClusters (radius,
+    and either minSize or keep='largest')"""
     arr = (Action * max(1, len(actions)))()
     keep = []
     for a, act in zip(arr, actions):
@@ -507,6 +513,12 @@ def make_actions(actions):
             a.kind, a.neighbors = ACTION_FILTER_OUTLIERS, (int(kk) if int(kk) == kk and abs(kk) < 2 ** 31 else 0)  # 0: refused
             a.outlier_mode = OUTLIER_SIGMA if 'sigma' in act else OUTLIER_DISTANCE
             a.outlier_value = float(act['sigma'] if 'sigma' in act else act['distance'])
+        elif k == 'filterClusters':
+            if 'radius' not in act or ('minSize' in act) == ('keep' in act) or act.get('keep', 'largest') != 'largest':
+                raise ValueError("filterClusters takes radius and either minSize or keep='largest'")
+            a.kind, a.cluster_radius = ACTION_FILTER_CLUSTERS, float(act['radius'])
+            a.cluster_mode = CLUSTER_LARGEST if 'keep' in act else CLUSTER_MIN_SIZE
+            a.cluster_min = float(act.get('minSize', 0))
         else:
             raise ValueError(k)
     arr._keep = keep
@@ -538,7 +550,7 @@ def process_schema(items, actions, with_source=False):
 TRANSFORM_KINDS = ('translate', 'rotate', 'scale')
 # the kinds that copy the table (those after filterByValue are this project's own)
 FILTER_KINDS = ('filterNaN', 'filterByValue', 'filterBox', 'filterSphere', 'decimate', 'orderByImportance',
-                'filterOutliers')
+                'filterOutliers', 'filterClusters')
 
 
 def sog_geometry(n, sh_coeffs):
@@ -1229,6 +1241,29 @@ class Context:
         placed, leaves, levels, pairs (d2 evaluations), nodes (box tests)"""
         import json
         return json.loads(lib().st_ctx_last_neighbor_stats(self.h).decode())
+
+    def dev_clusters(self, cols, radius):
+        """st_dev_clusters: the connected components of device columns (list of (name, tensor) or a dict;
+        x, y, z of any of the eight types) linked at `radius` (st_abi.h, "clusters") -> (label, size),
+        uint32 tensors: the smallest row index of the row's component (0xFFFFFFFF: not placed) and the
+        component's row count (0: not placed)"""
+        import torch
+        t = make_ttable(cols)
+        label = torch.empty(t.n, dtype=torch.uint32, device=f'cuda:{self.device}')
+        size = torch.empty(t.n, dtype=torch.uint32, device=f'cuda:{self.device}')
+        check(lib().st_dev_clusters(self.h, ctypes.byref(t), ctypes.c_double(float(radius)), _ptr(label), _ptr(size)))
+        return label, size
+
+    def clusters(self, cols, radius):
+        """the same of host columns (numpy arrays), uploaded -> (label, size) as uint32 arrays"""
+        label, size = self.dev_clusters(self._upload(cols), radius)
+        return label.cpu().numpy().view(np.uint32), size.cpu().numpy().view(np.uint32)
+
+    def last_cluster_stats(self):
+        """the last cluster search's sizes and work (st_ctx_last_cluster_stats) as a dict: rows, placed,
+        components, largest, leaves, levels, pairs (d2 evaluations), nodes (box tests), unions"""
+        import json
+        return json.loads(lib().st_ctx_last_cluster_stats(self.h).decode())
 
     def summary_stats(self):
         """the last summary's sum paths (st_ctx_last_summary_stats) as a dict: columns, fast, general,
